@@ -1,7 +1,14 @@
 """Benchmark: timesteps/s of the 2-layer Phillips hot path (evolve_zeta! + evolve_psi!) on
 MI355X, with the HBM roofline of the dominant kernel and the CPU oracle timed beside it.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--n 4096] [--dt 60]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--n 4096] [--dt 60] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: set-up, warm-up, the K timed
+steps, the outputs of the last timed step if --dump-outputs asks for them, the JSON line.
+Everything else the benchmark measures -- the PCG and multigrid-PCG legs, the per-kernel event
+pass and the live PMC traffic behind `roofline`, the drop-in legs, the reference's own benchmark
+configuration, the CPU oracle, and for N > 1 the collectives in isolation and the overlap /
+transport A/B legs -- runs only with --full (each leg keeps its own switch there).
 
 N > 1 runs one process per GPU: under torch.distributed.run (RANK / WORLD_SIZE from the
 environment), or, launched plainly with WORLD_SIZE unset, bench.py starts the N rank
@@ -17,14 +24,26 @@ Workload (BASELINE.json configs[2]; per GPU for N > 1, slabs in y, weak scaling)
   Lx = 4000 km per GPU, U = 0.1, nu = 100, r = 1e-7, R_d = 40 km, kick = 1e-6) with a stable
   dt = 60 s, seeded synthetic initial conditions.  A "step" is one timestep of the model:
   the fused tendency + AB3 kernel, then the Poisson + Helmholtz inversion.  The timed steps
-  are AB3 steps (the two Euler steps are inside the warm-up when W >= 2).
+  are AB3 steps (the two Euler steps are inside the warm-up: at least 3 warm-up steps run).
+  The GPU clock is brought up first (--clock-warm-ms, a number of steps that depends on the
+  box); then the state is initialised again from its seeds, so the W warm-up steps and the K
+  timed steps are always steps 1 .. W + K of the same initial state, whatever the box.
 
 Output: one JSON line (rank 0).  `value` is whole-job throughput = (GPUs x steps) / time,
-i.e. N x N-slab timesteps per second summed over GPUs (a single GPU: model timesteps/s).
-The timed region is exactly K steps enqueued by one qg_run call; the per-kernel HIP events
-(roofline) are recorded in a second pass over the next K steps, because every event record
-adds ~5 us of queue time (A/B on one MI355X: 4096^2 1588 vs 1531 steps/s, 1024^2 11 974 vs
-10 645 with the events inside the timed loop; tools/graph_vs_stream.sh).
+i.e. N x N-slab timesteps per second summed over GPUs (a single GPU: model timesteps/s);
+`ms_per_step` is the time of one timed step.  The timed region is exactly K steps enqueued by
+one qg_run call.  With --full the per-kernel HIP events (roofline) are recorded in a second
+pass over the next K steps, because every event record adds ~5 us of queue time (A/B on one
+MI355X: 4096^2 1588 vs 1531 steps/s, 1024^2 11 974 vs 10 645 with the events inside the timed
+loop; tools/graph_vs_stream.sh); without it `roofline` is the whole step's algorithmic HBM
+traffic over the timed region.
+
+--dump-outputs DIR writes what the timed steps left, as a caller of qg_run holds it after the
+last of them: the newest slot of zeta, psi and f_store (both layers, ghost cells included) as
+DIR/zeta.npy, DIR/psi.npy, DIR/f_store.npy in the state's precision (float64, or float32 with
+--dtype f32; rank 0's slab for N > 1).  An array of more than DUMP_MAX_ELEMS elements is
+written as a fixed sample of that many of its elements (seeded indices into the flattened
+array, the same in every run), so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -52,19 +71,28 @@ def bytes_per_point(B):
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--steps", type=int, default=50, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=20,
-                    help="untimed steps first (the GPU clock takes ~15 steps of 4096^2 to settle)")
+                    help="untimed steps right before the timed ones (at least 3 are run)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg of the benchmark (PCG and multigrid-PCG solvers, per-kernel "
+                         "events and live PMC traffic for the roofline, drop-in signatures, the reference's own "
+                         "benchmark configuration, the CPU oracle; N > 1: the collectives in isolation and the "
+                         "overlap / transport A/B legs).  Off: only the headline is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the newest zeta, psi and f_store as DIR/<name>.npy "
+                         "(a fixed seeded sample of an array larger than DUMP_MAX_ELEMS elements)")
     ap.add_argument("--clock-warm-ms", type=float, default=2000.0,
-                    help="after the W warm-up steps, keep stepping (untimed) until this much wall "
-                         "time of GPU work has passed, so the timed region never sits in the clock ramp "
-                         "(2 s: also long enough for a 1 Hz SMI sampler to see the GPU busy)")
+                    help="before the W warm-up steps, step (untimed) until this much wall time of GPU "
+                         "work has passed, so the timed region never sits in the clock ramp (2 s: also long "
+                         "enough for a 1 Hz SMI sampler to see the GPU busy); the state is initialised "
+                         "again afterwards")
     ap.add_argument("--n", "--grid", dest="n", type=int, default=4096, help="grid points per side per GPU")
     ap.add_argument("--dt", type=float, default=60.0)
     ap.add_argument("--chunk-rows", type=int, default=0)
-    ap.add_argument("--cpu-steps", type=int, default=10, help="CPU-oracle sample steps (0 = skip)")
+    ap.add_argument("--cpu-steps", type=int, default=10, help="--full: CPU-oracle sample steps (0 = skip)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = all threads OpenMP offers")
-    ap.add_argument("--cpu-steps-1t", type=int, default=2, help="single-thread CPU-oracle sample steps")
+    ap.add_argument("--cpu-steps-1t", type=int, default=2, help="--full: single-thread CPU-oracle sample steps")
     ap.add_argument("--solver", choices=("spectral", "pcg"), default="spectral",
                     help="streamfunction inversion: direct spectral (default) or matrix-free PCG "
                          "preconditioned by the spectral solve")
@@ -74,10 +102,10 @@ def parse(argv=None):
     ap.add_argument("--dtype", choices=("f64", "f32"), default="f64",
                     help="state precision: f64 (the reference's, default) or f32 (BASELINE config 5)")
     ap.add_argument("--pcg-steps", type=int, default=20,
-                    help="also time this many steps with the matrix-free PCG solver (single GPU, "
+                    help="--full: also time this many steps with the matrix-free PCG solver (single GPU, "
                          "spectral default only; 0 = skip)")
     ap.add_argument("--mg-steps", type=int, default=5,
-                    help="timed steps of the multigrid-preconditioned PCG leg (N = 1, F64; 0 = skip)")
+                    help="--full: timed steps of the multigrid-preconditioned PCG leg (N = 1, F64; 0 = skip)")
     ap.add_argument("--events-in-timed", action="store_true",
                     help="(A/B of the measurement) record the per-step HIP events inside the timed "
                          "region instead of in a separate pass")
@@ -112,24 +140,24 @@ def parse(argv=None):
                          "into every peer's IPC-mapped region; auto (default) = peer when the regions can "
                          "be set up on every rank, else rccl")
     ap.add_argument("--no-transport-ab", dest="transport_ab", action="store_false", default=True,
-                    help="N > 1 (or --comm-self): skip re-timing the K steps with RCCL's halo and gather "
+                    help="--full, N > 1 (or --comm-self): skip re-timing the K steps with RCCL's halo and gather "
                          "when the headline ran the peer transports (transport_ab)")
     ap.add_argument("--transport-ab-peer", action="store_true",
-                    help="N > 1 (or --comm-self) with an RCCL headline: re-time the K steps with the peer "
+                    help="--full, N > 1 (or --comm-self) with an RCCL headline: re-time the K steps with the peer "
                          "transports after the headline (opt-in: a fault in that leg would lose the "
                          "headline line)")
     ap.add_argument("--dropin-steps", type=int, default=20,
-                    help="also time this many steps through the reference's own array signatures "
+                    help="--full: also time this many steps through the reference's own array signatures "
                          "(evolve_zeta!(model, zeta, psi, t, f_store) / evolve_psi!(...) on bare arrays, "
                          "slot 1 newest after every call; single GPU, F64 spectral; 0 = skip)")
     ap.add_argument("--comm-probe-reps", type=int, default=20,
-                    help="N > 1 (or --comm-self): time the halo exchange and the record all-gather in "
+                    help="--full, N > 1 (or --comm-self): time the halo exchange and the record all-gather in "
                          "isolation, this many calls each (0 = skip); also re-times the K steps with the "
                          "halo overlap toggled (overlap_ab)")
     ap.add_argument("--comm-self", action="store_true",
                     help="single GPU through the multi-GPU path (1-rank RCCL ring): measures its overhead")
     ap.add_argument("--no-reference-runs", dest="reference_runs", action="store_false", default=True,
-                    help="N = 1: skip re-running the reference's own benchmark configuration (M = 8 ... 256, "
+                    help="--full, N = 1: skip re-running the reference's own benchmark configuration (M = 8 ... 256, "
                          "24 steps of dt = 60 min) beside its published Julia times (reference_benchmark)")
     ap.add_argument("--no-probe", dest="probe", action="store_false", default=True,
                     help="N > 1 over RCCL: skip the peer-transport probe group (below) and let the ranks "
@@ -141,10 +169,35 @@ def parse(argv=None):
     ap.add_argument("--probe-peer", action="store_true", help=argparse.SUPPRESS)   # (a probe rank)
     ap.add_argument("--probe-result", default=None, help=argparse.SUPPRESS)        # (launcher -> ranks)
     ap.add_argument("--no-pmc-live", dest="pmc_live", action="store_false", default=True,
-                    help="N = 1: skip measuring roofline.traffic live (two rocprofv3 --pmc child runs of "
+                    help="--full, N = 1: skip measuring roofline.traffic live (two rocprofv3 --pmc child runs of "
                          "this workload, FETCH_SIZE and WRITE_SIZE, ~20 s each); the committed "
                          "profiles/pmc_tendency.json is used instead")
     return ap.parse_args(argv)
+
+
+DUMP_MAX_ELEMS = 1 << 21  # per array: 3 arrays x 16 MiB of float64 at the most
+DUMP_SEED = 20240607
+
+
+def dump_outputs(st, torch, out_dir):
+    """--dump-outputs: the newest slot of zeta, psi and f_store, (2, P+2, M+2) each, as
+    out_dir/<name>.npy in the state's precision; an array of more than DUMP_MAX_ELEMS elements
+    as the elements at DUMP_MAX_ELEMS seeded indices of the flattened array (sorted, drawn
+    with replacement: the same indices in every run of the same size).  The caller has
+    synchronised the state.  Returns {name: [elements written, elements of the array]}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name in ("zeta", "psi", "f_store"):
+        a = getattr(st, name)[st.slot(name, 1)].reshape(-1)
+        total = a.numel()
+        if total > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, total, DUMP_MAX_ELEMS))
+            a = a[torch.from_numpy(idx).to(a.device)]
+        h = a.cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), h)
+        written[name] = [int(h.size), int(total)]
+    return written
 
 
 PMC_KERNEL = "tendency"  # substring of the dominant kernel's name (tendency_kernel / tendency_pair_kernel)
@@ -758,33 +811,35 @@ def main():
         dist.destroy_process_group()
         sys.exit(code)
 
-    # the north star's PCG leg first: real work on the same grid that also brings the GPU
-    # clock up before the measured model's warm-up (single GPU only)
+    # --full: the north star's PCG leg first: real work on the same grid that also brings the
+    # GPU clock up before the measured model's warm-up (single GPU only)
     pcg = None
-    if args.pcg_steps > 0 and world == 1 and args.solver == "spectral" and args.dtype == "f64":
+    if args.full and args.pcg_steps > 0 and world == 1 and args.solver == "spectral" and args.dtype == "f64":
         pcg = pcg_variant(qgamd, m, n, args.warmup, args.pcg_steps, torch, min(args.clock_warm_ms, 500.0))
     mg = None
-    if args.mg_steps > 0 and world == 1 and args.solver == "spectral" and args.dtype == "f64":
+    if args.full and args.mg_steps > 0 and world == 1 and args.solver == "spectral" and args.dtype == "f64":
         mg = mg_variant(qgamd, m, n, args.mg_steps, torch)
 
-    # W untimed warm-up steps (at least the 2 Euler steps + 1, so every timed step is an AB3
-    # step that reads F(t-1), F(t-2)), then untimed steps until >= --clock-warm-ms of GPU work
-    # have run: the clock settles over ~15 steps of 4096^2 (~10 ms) and a driver run with a
-    # small W would otherwise time the ramp.  The extra steps are reported (clock_warm_steps).
+    # untimed steps until >= --clock-warm-ms of GPU work have run: the clock settles over ~15
+    # steps of 4096^2 (~10 ms) and a run with a small W would otherwise time the ramp.  How
+    # many steps that takes depends on the box (reported: clock_warm_steps), so the state is
+    # initialised again afterwards.  Every rank must run the same number of steps (each step
+    # holds collectives): time one 4-step chunk, size the warm-up from it, agree on the largest
+    # count over ranks
     t = 1
-    for _ in range(max(args.warmup, 3)):
-        st.step(t)
-        t += 1
-    torch.cuda.synchronize()
-    # every rank must run the same number of steps (each step holds collectives): time one
-    # 4-step chunk, size the warm-up from it, agree on the largest count over ranks
     warm_steps = 0
     if args.clock_warm_ms > 0:
+        for _ in range(3):  # (the two Euler steps + 1)
+            st.step(t)
+            t += 1
+        st.run(t, 16)
+        t += 16
+        torch.cuda.synchronize()
         tw = time.perf_counter()
         st.run(t, 4)
         torch.cuda.synchronize()
         t += 4
-        warm_steps = 4
+        warm_steps = 23
         chunk_ms = (time.perf_counter() - tw) * 1e3
         chunks = max(0, int(args.clock_warm_ms / max(chunk_ms, 1e-3)))
         if dist is not None:
@@ -797,8 +852,17 @@ def main():
             t += 4 * chunks
             warm_steps += 4 * chunks
         torch.cuda.synchronize()
+        st.initialise()
+        t = 1
+    # W untimed warm-up steps (at least the 2 Euler steps + 1, so every timed step is an AB3
+    # step that reads F(t-1), F(t-2)): the timed steps are steps W + 1 .. W + K of the seeded
+    # initial state in every run
+    for _ in range(max(args.warmup, 3)):
+        st.step(t)
+        t += 1
+    torch.cuda.synchronize()
 
-    K = args.steps
+    K = max(args.steps, 1)
     # timed region: exactly K steps, enqueued by one qg_run call (the run_model_no_output loop,
     # in C), bracketed by barrier + synchronize; no events inside (each HIP event record costs
     # ~5 us of queue time on ROCm 7.2, ~2 % of a 4096^2 step, ~15 % at 1024^2)
@@ -806,7 +870,8 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     stream = torch.cuda.current_stream()
-    ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(K)]
+    events = args.full or args.events_in_timed
+    ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(K if events else 0)]
     t0 = time.perf_counter()
     if args.events_in_timed:
         for k in range(K):
@@ -827,9 +892,16 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         el = float(tt.item())
 
-    # kernel timing pass (same process, next K steps): HIP events on the library's stream
-    # around each evolve_zeta! (the tendency kernel alone on one GPU) and evolve_psi!
-    for k in range(K if not args.events_in_timed else 0):
+    # what the last timed step left (every rank completes its ghost rows, rank 0 writes)
+    dumped = None
+    if args.dump_outputs:
+        st.synchronize()
+        if rank == 0:
+            dumped = dump_outputs(st, torch, args.dump_outputs)
+
+    # --full: kernel timing pass (same process, next K steps): HIP events on the library's
+    # stream around each evolve_zeta! (the tendency kernel alone on one GPU) and evolve_psi!
+    for k in range(K if args.full and not args.events_in_timed else 0):
         ev[k][0].record(stream)
         st.evolve_zeta_(t)
         ev[k][1].record(stream)
@@ -838,15 +910,18 @@ def main():
         t += 1
     torch.cuda.synchronize()
 
-    step_ev_ms = sorted(e[0].elapsed_time(e[2]) for e in ev)
-    median_ms = step_ev_ms[K // 2]
-    tend_ms = sum(e[0].elapsed_time(e[1]) for e in ev) / K
-    solve_ms = sum(e[1].elapsed_time(e[2]) for e in ev) / K
+    median_ms = tend_ms = solve_ms = None
+    if events:
+        step_ev_ms = sorted(e[0].elapsed_time(e[2]) for e in ev)
+        median_ms = step_ev_ms[K // 2]
+        tend_ms = sum(e[0].elapsed_time(e[1]) for e in ev) / K
+        solve_ms = sum(e[1].elapsed_time(e[2]) for e in ev) / K
     finite = bool(torch.isfinite(st.current("psi", 1)).all().item())
 
-    # multi-GPU: the two collectives of a step timed in isolation, then the same K steps with
-    # the halo / interior overlap toggled (all ranks take part in both)
+    # --full, multi-GPU: the two collectives of a step timed in isolation, then the same K steps
+    # with the halo / interior overlap toggled (all ranks take part in both)
     comm, overlap_ab = None, None
+    comm_legs = args.full and args.comm_probe_reps > 0
     dev_red = "cuda" if args.transport == "rccl" else "cpu"
 
     def all_ok(ok):
@@ -859,7 +934,7 @@ def main():
         dist.all_reduce(f, op=dist.ReduceOp.MIN)
         return bool(f.item())
 
-    if args.comm_probe_reps > 0 and (world > 1 or args.comm_self) and args.solver == "spectral":
+    if comm_legs and (world > 1 or args.comm_self) and args.solver == "spectral":
         err = None
         try:
             comm = st.comm_probe(args.comm_probe_reps)
@@ -912,7 +987,7 @@ def main():
     transport_ab = None
     peer_now = (cur_halo, cur_gather) != ("rccl", "rccl")
     if args.transport_ab and args.transport == "rccl" and (world > 1 or args.comm_self) \
-            and args.solver == "spectral" and args.comm_probe_reps > 0 \
+            and args.solver == "spectral" and comm_legs \
             and (peer_now or (args.transport_ab_peer and not (transport_choice or "").startswith("rccl: peer"))):
         alt_h, alt_g, alt_ov = ("rccl", "rccl", True) if peer_now else ("put", "peer", False)
         err3, el3 = None, None
@@ -957,17 +1032,16 @@ def main():
     pts = n * n
     BYTES_TENDENCY_AB3, BYTES_SOLVE, BYTES_STEP = bytes_per_point(4 if args.dtype == "f32" else 8)
     ms = el * 1e3 / K
-    tend_gbs = BYTES_TENDENCY_AB3 * pts / (tend_ms * 1e-3) / 1e9
     step_gbs = BYTES_STEP * pts / (ms * 1e-3) / 1e9
     traffic, pmc_tag, traffic_source = None, None, None
-    if args.pmc_live and world == 1 and not args.comm_self and args.solver == "spectral":
+    if args.full and args.pmc_live and world == 1 and not args.comm_self and args.solver == "spectral":
         traffic, note = pmc_live(args)
         if traffic is not None:
             traffic_source = note
         else:
             print(f"bench: live PMC traffic unavailable ({note}); using the committed file", file=sys.stderr)
     prof = os.path.join(ROOT, "profiles", "pmc_tendency.json")
-    if traffic is None and os.path.exists(prof):
+    if events and traffic is None and os.path.exists(prof):
         try:
             pj = json.load(open(prof))
             if pj.get("n") == n and args.dtype == "f64" and args.solver == "spectral":
@@ -977,6 +1051,33 @@ def main():
                                   f"per launch, box {pmc_tag}")
         except Exception:
             traffic = None
+    if events:
+        tend_gbs = BYTES_TENDENCY_AB3 * pts / (tend_ms * 1e-3) / 1e9
+        roofline = {
+            "bound": "hbm",
+            "kernel": "tendency_kernel (fused Arakawa J + biharmonic + beta + AB3, both layers)",
+            "achieved": tend_gbs,
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": tend_gbs / HBM_PEAK_GBS,
+            "traffic": traffic,
+            "traffic_source": traffic_source if traffic is not None else None,
+            "avg_launch_ms": tend_ms,
+            "algorithmic_bytes_per_launch": BYTES_TENDENCY_AB3 * pts,
+        }
+    else:
+        # (no event pass: the whole step's algorithmic bytes over the timed region)
+        roofline = {
+            "bound": "hbm",
+            "kernel": "whole step (tendency + solve) over the timed region; the dominant kernel's own "
+                      "figures and its measured traffic come with --full",
+            "achieved": step_gbs,
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": step_gbs / HBM_PEAK_GBS,
+            "traffic": None,
+            "algorithmic_bytes_per_step": BYTES_STEP * pts,
+        }
     out = {
         "metric": METRIC,
         "value": world * K / el,
@@ -985,6 +1086,7 @@ def main():
         "steps": K,
         "warmup": args.warmup,
         "clock_warm_steps": warm_steps,
+        "full": bool(args.full),
         "ms_per_step": ms,
         "ms_per_step_median_events": median_ms,
         "setup_ms": setup_ms,
@@ -1018,18 +1120,7 @@ def main():
             "gather_transport": (cur_gather if args.transport == "rccl" and (world > 1 or args.comm_self)
                                  and args.solver == "spectral" else None),
         },
-        "roofline": {
-            "bound": "hbm",
-            "kernel": "tendency_kernel (fused Arakawa J + biharmonic + beta + AB3, both layers)",
-            "achieved": tend_gbs,
-            "peak": HBM_PEAK_GBS,
-            "unit": "GB/s",
-            "frac": tend_gbs / HBM_PEAK_GBS,
-            "traffic": traffic,
-            "traffic_source": traffic_source if traffic is not None else None,
-            "avg_launch_ms": tend_ms,
-            "algorithmic_bytes_per_launch": BYTES_TENDENCY_AB3 * pts,
-        },
+        "roofline": roofline,
         "step_roofline": {
             "achieved": step_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": step_gbs / HBM_PEAK_GBS,
             "algorithmic_bytes_per_step": BYTES_STEP * pts, "solve_ms": solve_ms, "tendency_ms": tend_ms,
@@ -1045,9 +1136,11 @@ def main():
         out["overlap_ab"] = overlap_ab
     if transport_ab is not None:
         out["transport_ab"] = transport_ab
-    if args.comm_probe_reps <= 0 and (world > 1 or args.comm_self) and args.solver == "spectral":
-        out["comm"] = out["overlap_ab"] = {"skipped": "--comm-probe-reps 0"}
-    if args.dropin_steps > 0 and world == 1 and args.solver == "spectral" and args.dtype == "f64" \
+    if not comm_legs and (world > 1 or args.comm_self) and args.solver == "spectral":
+        out["comm"] = out["overlap_ab"] = {"skipped": "--comm-probe-reps 0" if args.full else "not --full"}
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
+    if args.full and args.dropin_steps > 0 and world == 1 and args.solver == "spectral" and args.dtype == "f64" \
             and not args.comm_self:
         del st
         torch.cuda.empty_cache()
@@ -1058,12 +1151,12 @@ def main():
             except Exception as e:  # noqa: BLE001 -- reported, the headline line is still printed
                 d = {"error": f"{type(e).__name__}: {e}"}
             out[key] = d
-    if args.reference_runs and world == 1 and not args.comm_self:
+    if args.full and args.reference_runs and world == 1 and not args.comm_self:
         try:
             out["reference_benchmark"] = reference_benchmark(qgamd, torch)
         except Exception as e:  # noqa: BLE001 -- reported, the headline line is still printed
             out["reference_benchmark"] = {"error": f"{type(e).__name__}: {e}"}
-    if args.cpu_steps > 0 and world == 1 and args.dtype == "f64":
+    if args.full and args.cpu_steps > 0 and world == 1 and args.dtype == "f64":
         out["cpu_baseline"] = cpu_baseline(n, args.dt, args.cpu_steps, args.cpu_threads, args.cpu_steps_1t)
     else:
         out["cpu_baseline"] = None

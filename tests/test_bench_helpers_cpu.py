@@ -66,6 +66,75 @@ def test_verify_peer_falls_back_on_one_ulp():
     assert (st.halo_transport, st.gather_transport) == ("rccl", "rccl")
 
 
+class _DumpState:
+    """Stands in for qgamd.State: three rotating-slot arrays with the newest in slot 2."""
+
+    def __init__(self, P, M, dtype):
+        g = torch.Generator().manual_seed(1)
+        for name in ("zeta", "psi", "f_store"):
+            setattr(self, name, torch.rand(3, 2, P + 2, M + 2, generator=g, dtype=torch.float64).to(dtype))
+
+    def slot(self, which, logical):
+        assert logical == 1
+        return 2
+
+
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
+def test_dump_outputs_writes_newest_slot(tmp_path, dtype):
+    import numpy as np
+    st = _DumpState(6, 10, dtype)
+    got = bench.dump_outputs(st, torch, str(tmp_path / "d"))
+    for name in ("zeta", "psi", "f_store"):
+        a = np.load(tmp_path / "d" / f"{name}.npy")
+        assert a.dtype == (np.float64 if dtype == torch.float64 else np.float32)
+        assert np.array_equal(a, getattr(st, name)[2].reshape(-1).numpy())
+        assert got[name] == [2 * 8 * 12, 2 * 8 * 12]
+
+
+def test_dump_outputs_samples_a_large_array_the_same_way_every_time(tmp_path, monkeypatch):
+    import numpy as np
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 100)
+    st = _DumpState(30, 40, torch.float64)
+    got = bench.dump_outputs(st, torch, str(tmp_path / "a"))
+    bench.dump_outputs(st, torch, str(tmp_path / "b"))
+    total = 2 * 32 * 42
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, total, 100))
+    for name in ("zeta", "psi", "f_store"):
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.shape == (100,) and np.array_equal(a, b)
+        assert np.array_equal(a, getattr(st, name)[2].reshape(-1).numpy()[idx])
+        assert got[name] == [100, total]
+
+
+def test_dump_sample_is_ordered_elements_spread_over_the_array(tmp_path, monkeypatch):
+    """Independent of how the indices are drawn: with every element equal to its own flat index,
+    the sample holds valid indices in ascending order that cover most of the array, the same
+    ones for all three arrays."""
+    import numpy as np
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 64)
+    st = _DumpState(30, 40, torch.float64)
+    total = 2 * 32 * 42
+    for name in ("zeta", "psi", "f_store"):
+        getattr(st, name)[2] = torch.arange(total, dtype=torch.float64).reshape(2, 32, 42)
+    bench.dump_outputs(st, torch, str(tmp_path))
+    a = np.load(tmp_path / "zeta.npy")
+    assert a.shape == (64,) and np.all(a == np.round(a)) and a.min() >= 0 and a.max() < total
+    assert np.all(np.diff(a) >= 0) and len(np.unique(a)) > 48 and a.max() - a.min() > total / 2
+    assert np.array_equal(a, np.load(tmp_path / "psi.npy")) and np.array_equal(a, np.load(tmp_path / "f_store.npy"))
+
+
+def test_dump_stays_under_its_size_limit_at_the_benchmark_size():
+    # three arrays of at most DUMP_MAX_ELEMS float64 elements: under 64 MB in all
+    assert 3 * bench.DUMP_MAX_ELEMS * 8 < 64e6
+
+
+def test_plain_run_is_the_default():
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not a.full and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse(["--full", "--dump-outputs", "x"])
+    assert a.full and a.dump_outputs == "x"
+
+
 def test_reference_benchmark_configuration():
     """reference_benchmark re-runs the reference's own benchmark configuration
     (benchmarking.jl: dt = 60 min, T = 1 day -> 24 steps, M = P = 8 ... 256) and sets the

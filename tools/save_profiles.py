@@ -17,7 +17,9 @@ tag, rnd = sys.argv[1], sys.argv[2]
 g = os.path.join(ROOT, "gpurun_out")
 d = os.path.join(ROOT, "profiles", rnd)
 os.makedirs(d, exist_ok=True)
-shutil.copy(os.path.join(g, f"bench_{tag}.json"), os.path.join(d, f"bench_{tag}.json"))
+# (the bench record: where tools/gpu_check.sh wrote it, $OUT or bench_out/)
+b = os.path.join(ROOT, os.environ.get("OUT", "bench_out"))
+shutil.copy(os.path.join(b, f"bench_{tag}.json"), os.path.join(d, f"bench_{tag}.json"))
 shutil.copy(os.path.join(g, f"prof_{tag}", f"{tag}_kernel_stats.csv"), os.path.join(d, f"{tag}_kernel_stats.csv"))
 subprocess.run([sys.executable, os.path.join(ROOT, "tools", "pmc_to_json.py"), tag, "4096"], check=True,
                stdout=subprocess.DEVNULL)
