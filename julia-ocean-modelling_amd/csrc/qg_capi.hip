@@ -190,6 +190,17 @@ static int check_params(const qg_params *p) {
     return QG_OK;
 }
 
+extern "C++" {
+// qg_create's host-side checks (no device call), shared with the other handles built on qg_params
+int qg::check_create_params(const qg_params *p) {
+    QG_CHECK(check_params(p));
+    const Derived d = derive(*p);
+    // beta_1 and beta_2 must have opposite signs (model.jl:38)
+    if (!((d.beta1 > 0 && d.beta2 < 0) || (d.beta1 < 0 && d.beta2 > 0))) return QG_ERR_INVALID_ARG;
+    return QG_OK;
+}
+}  // extern "C++"
+
 // the wind row table of this rank's slab (built on first use; rebuilt after a comm attach)
 static int ensure_wind(qg_ctx *c) {
     const qg_params &p = c->p;
@@ -240,7 +251,7 @@ static int build_solver(qg_ctx *c) {
 int qg_create(const qg_params *p, int device, void *stream, qg_ctx **out) {
     if (!out) return QG_ERR_INVALID_ARG;
     *out = nullptr;
-    QG_CHECK(check_params(p));
+    QG_CHECK(check_create_params(p));
     qg_ctx *c = new (std::nothrow) qg_ctx();
     if (!c) return QG_ERR_ALLOC;
     c->p = *p;
@@ -249,11 +260,6 @@ int qg_create(const qg_params *p, int device, void *stream, qg_ctx **out) {
     c->stream = static_cast<hipStream_t>(stream);
     c->F = (size_t)(p->M + 2) * (size_t)(p->P + 2);
     c->esize = p->dtype == QG_F32 ? sizeof(float) : sizeof(double);
-    // beta_1 and beta_2 must have opposite signs (model.jl:38)
-    if (!((c->d.beta1 > 0 && c->d.beta2 < 0) || (c->d.beta1 < 0 && c->d.beta2 > 0))) {
-        delete c;
-        return QG_ERR_INVALID_ARG;
-    }
     int st = build_solver(c);
     if (st != QG_OK) {
         delete c;

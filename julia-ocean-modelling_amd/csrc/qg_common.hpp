@@ -39,6 +39,8 @@ int comm_wait(void *comm, hipStream_t s, hipEvent_t ev, const char *what);
 // qg_set_form's value for `which` (QG_FORM_*; 0 = the automatic choice)
 int form(int which);
 int comm_set_timeout(void *comm, double seconds);
+// the parameter checks of qg_create (qg_capi.hip): host only, before any device call
+int check_create_params(const qg_params *p);
 
 __host__ __device__ inline size_t fidx(int64_t i, int64_t j, int64_t ld) {
     return static_cast<size_t>(i) + static_cast<size_t>(ld) * static_cast<size_t>(j);
@@ -240,6 +242,9 @@ inline double wind_row(double tau0, double rho0, double H1, double dx, int64_t P
 
 int launch_tendency(const TendArgsT<double> &a, hipStream_t s);
 int launch_tendency(const TendArgsT<float> &a, hipStream_t s);
+// ensembles: rows [j0, j1) of nmembers members in one launch of the cache-resident one-point
+// form; member b's fields lie b * member_stride elements behind the pointers of `a`
+int launch_tendency_members(const TendArgsT<double> &a, int nmembers, int64_t member_stride, hipStream_t s);
 // the same tendency, both layers per workgroup, also certifying the previous solve (a.cert):
 // *nblk = workgroups launched (partials written); a grid of more than `cap` workgroups (the
 // partials' capacity) is refused before anything is launched

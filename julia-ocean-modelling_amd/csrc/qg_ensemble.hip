@@ -1,0 +1,253 @@
+// Batched initial-condition ensembles (include/qg_mi355_ensemble.h): nmembers instances of one
+// model advanced by the four launches per step one qg_ctx needs for one instance.
+//
+// The state arrays are (M+2, P+2, 2, 3, nmembers), member slowest, so member b's block is a
+// single context's array at element offset b * 6 F (F = (M+2)(P+2)).  A step is
+//   launch_tendency_members   the cache-resident one-point tendency over (x, rows, layer, member)
+//   SpectralSolver::solve_members   pass A, carry (fused pin), pass B, each over (.., member)
+// with the slot rotation of qg_step (keep-order off) and one set of heads for all members.
+// Shared: parameters, the wind table, the solver's twiddles and coefficient tables.  Per member:
+// the state and the solver's scratch.  Per-point arithmetic and chunking are a single
+// context's, so every member's bits are a single context's.
+#include <cstring>
+#include <memory>
+#include <new>
+#include <vector>
+
+#include "qg_common.hpp"
+#include "qg_mi355_ensemble.h"
+#include "qg_spectral.hpp"
+
+namespace qg {
+int diag_record_len();
+size_t diag_scratch_doubles();
+int launch_diagnostics(const void *z0, const void *z1, const void *p0, const void *p1, int esize, int64_t M,
+                       int64_t P, double dx, double *scratch, double *rec, hipStream_t s);
+}  // namespace qg
+
+using namespace qg;
+
+struct qg_ens {
+    qg_params p{};
+    Derived d{};
+    int device = 0;
+    hipStream_t stream = nullptr;
+    int nmembers = 0;
+    double *zeta = nullptr, *psi = nullptr, *fst = nullptr;
+    int heads[3] = {0, 0, 0};  // physical slot of logical slot 1 for zeta, psi, f_store (all members)
+    double *wind = nullptr;    // [P] wind forcing of the rows (qg_params.wind_tau0 != 0)
+    double *diag = nullptr;    // diagnostics: partial records (reused member after member) | nmembers records
+    SpectralSolver spec;
+    size_t F = 0;  // doubles per (M+2, P+2) field
+
+    size_t member_stride() const { return 6 * F; }  // doubles between two members' blocks
+    double *field(double *base, int layer, int slot) const { return base + F * (size_t)(layer + 2 * slot); }
+};
+
+extern "C" {
+
+int qg_ens_create(const qg_params *p, int nmembers, int device, void *stream, qg_ens **out) {
+    if (!out) return QG_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (nmembers < 1 || nmembers > QG_ENS_MAX_MEMBERS) return QG_ERR_INVALID_ARG;
+    QG_CHECK(check_create_params(p));
+    if (p->dtype != QG_F64 || p->solver != QG_SOLVER_SPECTRAL) return QG_ERR_UNSUPPORTED;
+    if (!SpectralSolver::supports_members(p->M, p->P, 1, 0)) return QG_ERR_UNSUPPORTED;
+    qg_ens *e = new (std::nothrow) qg_ens();
+    if (!e) return QG_ERR_ALLOC;
+    e->p = *p;
+    e->d = derive(*p);
+    e->device = device;
+    e->stream = static_cast<hipStream_t>(stream);
+    e->nmembers = nmembers;
+    e->F = (size_t)(p->M + 2) * (size_t)(p->P + 2);
+    auto build = [&]() -> int {
+        QG_HIP(hipSetDevice(device));
+        if (p->wind_tau0 != 0) {
+            std::vector<double> w((size_t)p->P);
+            for (int64_t j = 0; j < p->P; ++j) w[j] = wind_row(p->wind_tau0, p->wind_rho0, p->H_1, p->dx, p->P, j);
+            if (hipMalloc((void **)&e->wind, sizeof(double) * p->P) != hipSuccess) return QG_ERR_ALLOC;
+            QG_HIP(hipMemcpy(e->wind, w.data(), sizeof(double) * p->P, hipMemcpyHostToDevice));
+        }
+        const double alpha[2] = {0.0, e->d.Seig};
+        QG_CHECK(e->spec.init(p->M, p->P, p->P, 0, 1, p->dx, alpha, 1, e->d.Pinv, p->P_fwd, p->chunk_rows, 0,
+                              nmembers));
+        const size_t nd = diag_scratch_doubles() + (size_t)diag_record_len() * nmembers;
+        if (hipMalloc((void **)&e->diag, sizeof(double) * nd) != hipSuccess) return QG_ERR_ALLOC;
+        return QG_OK;
+    };
+    const int st = build();
+    if (st != QG_OK) {
+        qg_ens_destroy(e);
+        return st;
+    }
+    *out = e;
+    return QG_OK;
+}
+
+int qg_ens_destroy(qg_ens *e) {
+    if (!e) return QG_OK;
+    (void)hipSetDevice(e->device);
+    if (e->wind) (void)hipFree(e->wind);
+    if (e->diag) (void)hipFree(e->diag);
+    delete e;
+    return QG_OK;
+}
+
+int qg_ens_members(const qg_ens *e, int *nmembers) {
+    if (!e || !nmembers) return QG_ERR_INVALID_ARG;
+    *nmembers = e->nmembers;
+    return QG_OK;
+}
+
+int qg_ens_bind_state(qg_ens *e, void *zeta, void *psi, void *f_store) {
+    if (!e || !zeta || !psi || !f_store) return QG_ERR_INVALID_ARG;
+    for (const void *b : {zeta, psi, f_store})  // (launch_slot_move's 16-byte vectors)
+        if (reinterpret_cast<uintptr_t>(b) % 16 != 0) return QG_ERR_INVALID_ARG;
+    e->zeta = static_cast<double *>(zeta);
+    e->psi = static_cast<double *>(psi);
+    e->fst = static_cast<double *>(f_store);
+    e->heads[0] = e->heads[1] = e->heads[2] = 0;
+    return QG_OK;
+}
+
+int qg_ens_initialise(qg_ens *e, const uint64_t *seed1, const uint64_t *seed2) {
+    if (!e || !seed1 || !seed2) return QG_ERR_INVALID_ARG;
+    if (!e->zeta) return QG_ERR_NOT_BOUND;
+    const qg_params &p = e->p;
+    QG_HIP(hipSetDevice(e->device));
+    const double amp = p.initial_kick * p.U * p.Ly;
+    for (int b = 0; b < e->nmembers; ++b) {
+        const size_t o = e->member_stride() * (size_t)b;
+        QG_CHECK(launch_initialise_global(e->zeta + o, e->psi + o, e->fst + o, (int)sizeof(double), p.M, p.P, p.P, 0,
+                                          amp, e->d.S1, e->d.S2, p.dx, seed1[b], seed2[b], e->stream));
+    }
+    e->heads[0] = e->heads[1] = e->heads[2] = 0;
+    return QG_OK;
+}
+
+// evolve_zeta! of every member (rotating slots: the new values go to the oldest slot)
+static int ens_evolve_zeta(qg_ens *e, int64_t timestep) {
+    const qg_params &p = e->p;
+    const int zh = e->heads[0], ph = e->heads[1], fh = e->heads[2], fh2 = (fh + 1) % 3;
+    const int zn = (zh + 2) % 3, fn = (fh + 2) % 3;
+    TendArgs a{};
+    a.M = p.M;
+    a.P = p.P;
+    a.ld = p.M + 2;
+    a.dx = p.dx;
+    a.visc = p.visc;
+    a.dt = p.dt;
+    a.U = p.U;
+    a.r = p.r;
+    a.beta[0] = e->d.beta1;
+    a.beta[1] = e->d.beta2;
+    a.ab3 = timestep >= 3;
+    a.j0 = 0;
+    a.j1 = (int)p.P;
+    a.write_ghost_rows = 1;
+    a.wind = e->wind;
+    // rows -2, -1, P, P+1 are the periodic images P-2, P-1, 0, 1
+    const int64_t P = p.P, ld = p.M + 2;
+    const int64_t rows[4] = {(P - 2 + P) % P, P - 1, 0, 1 % P};
+    for (int l = 0; l < 2; ++l) {
+        a.zeta[l] = e->field(e->zeta, l, zh);
+        a.psi[l] = e->field(e->psi, l, ph);
+        a.fprev1[l] = e->field(e->fst, l, fh);
+        a.fprev2[l] = e->field(e->fst, l, fh2);
+        a.zeta_out[l] = e->field(e->zeta, l, zn);
+        a.f_out[l] = e->field(e->fst, l, fn);
+        for (int h = 0; h < 4; ++h) {
+            a.zeta_rows[l].halo[h] = a.zeta[l] + fidx(1, rows[h] + 1, ld);
+            a.psi_rows[l].halo[h] = a.psi[l] + fidx(1, rows[h] + 1, ld);
+        }
+    }
+    QG_CHECK(launch_tendency_members(a, e->nmembers, (int64_t)e->member_stride(), e->stream));
+    e->heads[0] = zn;
+    e->heads[2] = fn;
+    return QG_OK;
+}
+
+// evolve_psi! of every member
+static int ens_evolve_psi(qg_ens *e) {
+    const int zh = e->heads[0], pn = (e->heads[1] + 2) % 3;
+    QG_CHECK(e->spec.solve_members(e->field(e->zeta, 0, zh), e->field(e->zeta, 1, zh), e->field(e->psi, 0, pn),
+                                   e->field(e->psi, 1, pn), (int64_t)(sizeof(double) * e->member_stride()),
+                                   e->stream));
+    e->heads[1] = pn;
+    return QG_OK;
+}
+
+int qg_ens_step(qg_ens *e, int64_t timestep) {
+    if (!e || timestep < 1) return QG_ERR_INVALID_ARG;
+    if (!e->zeta) return QG_ERR_NOT_BOUND;
+    QG_HIP(hipSetDevice(e->device));
+    QG_CHECK(ens_evolve_zeta(e, timestep));
+    return ens_evolve_psi(e);
+}
+
+int qg_ens_run(qg_ens *e, int64_t first_step, int64_t nsteps) {
+    if (!e || first_step < 1 || nsteps < 0) return QG_ERR_INVALID_ARG;
+    if (!e->zeta) return QG_ERR_NOT_BOUND;
+    for (int64_t t = first_step; t < first_step + nsteps; ++t) QG_CHECK(qg_ens_step(e, t));
+    return QG_OK;
+}
+
+int qg_ens_slot(const qg_ens *e, int which, int logical, int *physical) {
+    if (!e || !physical || which < 0 || which > 2 || logical < 1 || logical > 3) return QG_ERR_INVALID_ARG;
+    *physical = (e->heads[which] + logical - 1) % 3;
+    return QG_OK;
+}
+
+int qg_ens_canonicalize(qg_ens *e) {
+    if (!e) return QG_ERR_INVALID_ARG;
+    if (!e->zeta) return QG_ERR_NOT_BOUND;
+    QG_HIP(hipSetDevice(e->device));
+    // per member, one launch rotates every field whose newest slot is not physical 0 (qg_canonicalize)
+    int src[3][3], which[3], n = 0;
+    for (int w = 0; w < 3; ++w) {
+        if (e->heads[w] == 0) continue;
+        which[n] = w;
+        for (int q = 0; q < 3; ++q) src[n][q] = (e->heads[w] + q) % 3;
+        ++n;
+    }
+    double *bases[3] = {e->zeta, e->psi, e->fst};
+    for (int b = 0; n && b < e->nmembers; ++b) {
+        void *arr[3];
+        for (int k = 0; k < n; ++k) arr[k] = bases[which[k]] + e->member_stride() * (size_t)b;
+        QG_CHECK(launch_slot_move(arr, src, n, 2 * sizeof(double) * e->F, e->stream));
+    }
+    e->heads[0] = e->heads[1] = e->heads[2] = 0;
+    return QG_OK;
+}
+
+int qg_ens_diagnostics(qg_ens *e, qg_diag *out) {
+    if (!e || !out) return QG_ERR_INVALID_ARG;
+    if (!e->zeta) return QG_ERR_NOT_BOUND;
+    constexpr int NREC = (int)(sizeof(qg_diag) / sizeof(double));
+    if (diag_record_len() != NREC) return QG_ERR_UNSUPPORTED;
+    QG_HIP(hipSetDevice(e->device));
+    const int zh = e->heads[0], ph = e->heads[1];
+    double *recs = e->diag + diag_scratch_doubles();
+    // a single context's two launches per member (same geometry: the same sums), one record each;
+    // the partials are reused in stream order
+    for (int b = 0; b < e->nmembers; ++b) {
+        const size_t o = e->member_stride() * (size_t)b;
+        QG_CHECK(launch_diagnostics(e->field(e->zeta, 0, zh) + o, e->field(e->zeta, 1, zh) + o,
+                                    e->field(e->psi, 0, ph) + o, e->field(e->psi, 1, ph) + o, (int)sizeof(double),
+                                    e->p.M, e->p.P, e->p.dx, e->diag, recs + (size_t)NREC * b, e->stream));
+    }
+    QG_HIP(hipMemcpyAsync(out, recs, sizeof(qg_diag) * (size_t)e->nmembers, hipMemcpyDeviceToHost, e->stream));
+    QG_HIP(hipStreamSynchronize(e->stream));
+    for (int b = 0; b < e->nmembers; ++b) out[b].reserved = 0.0;
+    return QG_OK;
+}
+
+int qg_ens_synchronize(qg_ens *e) {
+    if (!e) return QG_ERR_INVALID_ARG;
+    QG_HIP(hipSetDevice(e->device));
+    QG_HIP(hipStreamSynchronize(e->stream));
+    return QG_OK;
+}
+
+}  // extern "C"

@@ -67,10 +67,53 @@ __device__ __forceinline__ double2 cfma(double s, double2 x, double2 y) {  // s*
 #define QG_CR(o) a.cr[o]
 
 // ------------------------------------------------------------------------------------
+// Ensembles (qg_mi355_ensemble.h): B members of one model solved by the same three launches.
+// The member is an added grid dimension; the tables (tw, coef, crr, ccs, cr) are shared, the
+// per-solve scratch (U .. pinpart, one block of `scratch` bytes per member, laid out like
+// member 0's) and the fields (members `field` bytes apart) are the member's own.  Each
+// workgroup runs the single-context body on its member's pointers with the single context's
+// chunking, so a member's bits are those of a single context.
+// ------------------------------------------------------------------------------------
+struct SpecEns {
+    int64_t scratch;  // bytes between two members' scratch blocks
+    int64_t field;    // bytes between two members' (M+2, P+2) fields (inputs and outputs)
+};
+
+template <class T>
+__device__ __forceinline__ T *ens_off(T *p, int64_t bytes) {
+    return reinterpret_cast<T *>(reinterpret_cast<uintptr_t>(p) + (uintptr_t)bytes);
+}
+
+__device__ __forceinline__ SpecArgs spec_member(const SpecArgs &a, const SpecEns &e, int b) {
+    SpecArgs m = a;
+    const int64_t so = e.scratch * b, fo = e.field * b;
+    m.in1 = ens_off(a.in1, fo);
+    m.in2 = ens_off(a.in2, fo);
+    m.out1 = ens_off(a.out1, fo);
+    m.out2 = a.out2 ? ens_off(a.out2, fo) : nullptr;
+    m.U = ens_off(a.U, so);
+    m.ULS = ens_off(a.ULS, so);
+    m.WLS = ens_off(a.WLS, so);
+    m.UIN = ens_off(a.UIN, so);
+    m.WIN = ens_off(a.WIN, so);
+    m.dcpart = ens_off(a.dcpart, so);
+    m.rec = ens_off(a.rec, so);
+    m.grec = m.rec;  // one rank
+    m.EXT = ens_off(a.EXT, so);
+    m.hline = ens_off(a.hline, so);
+    m.line = ens_off(a.line, so);
+    m.scal = ens_off(a.scal, so);
+    m.pinpart = ens_off(a.pinpart, so);
+    return m;
+}
+
+// ------------------------------------------------------------------------------------
 // pass A: project + row DFT + chunk-local backward filter (one workgroup per chunk)
 // ------------------------------------------------------------------------------------
-template <int N, class S>
-__global__ __launch_bounds__(Geo<N>::T, Geo<N>::MINW) void spec_passA(SpecArgs a) {
+// (E: empty for a single context; SpecEns for an ensemble, grid (chunks, members))
+template <int N, class S, class... E>
+__global__ __launch_bounds__(Geo<N>::T, Geo<N>::MINW) void spec_passA(SpecArgs a, E... ens) {
+    if constexpr (sizeof...(E) > 0) a = spec_member(a, ens..., (int)blockIdx.y);
     using US = typename Store<S>::C;
     using G = Geo<N>;
     constexpr int T = G::T, KQ = G::KQ, EP = G::EP, NH = N / 2;
@@ -490,8 +533,10 @@ constexpr int CARRY_REG = 8;  // chunks per segment held in registers
 // with more carry workgroups than CUs (M = 4096: 2 x 129 + 2 = 260 on 256 CUs left 4 of them
 // for a second round; with two per CU 26.0 -> 21.8 us despite a small spill).  Smaller M keeps
 // 1 (no spill: 1024^2 11.8 vs 13.5 us).
-template <int MINW>
-__global__ __launch_bounds__(64 * CARRY_WAVES, MINW) void spec_carry(SpecArgs a) {
+// (E: see spec_passA; ensembles: the member is blockIdx.z)
+template <int MINW, class... E>
+__global__ __launch_bounds__(64 * CARRY_WAVES, MINW) void spec_carry(SpecArgs a, E... ens) {
+    if constexpr (sizeof...(E) > 0) a = spec_member(a, ens..., (int)blockIdx.z);
     __shared__ double2 agg[CARRY_SEG][CARRY_KB];
     __shared__ double qlen_s[CARRY_SEG][CARRY_KB];
     constexpr int NT = 64 * CARRY_WAVES;
@@ -733,8 +778,10 @@ __device__ __forceinline__ void chunk_carry(const SpecArgs &a, int s, int k, int
     carry_in(a, cf, s, c, delta, inject, Ue, We, a.UIN[o], a.WIN[o], cu, w);
 }
 
-template <int N, class S>
-__global__ __launch_bounds__(Geo<N>::T, Geo<N>::MINW) void spec_passB(SpecArgs a) {
+// (E: see spec_passA; ensembles: grid (chunks, members))
+template <int N, class S, class... E>
+__global__ __launch_bounds__(Geo<N>::T, Geo<N>::MINW) void spec_passB(SpecArgs a, E... ens) {
+    if constexpr (sizeof...(E) > 0) a = spec_member(a, ens..., (int)blockIdx.y);
     using US = typename Store<S>::C;
     using G = Geo<N>;
     constexpr int T = G::T, KQ = G::KQ, EP = G::EP, NH = N / 2;
@@ -2381,6 +2428,37 @@ static int launch_pass(bool passB, const SpecArgs &a, hipStream_t s) {
     return a.f32 ? launch_pass_t<N, float>(passB, a, s) : launch_pass_t<N, double>(passB, a, s);
 }
 
+// the batched passes of an ensemble (F64, M = 2^k in 8..2048): grid (chunks, members)
+template <int N>
+static int launch_pass_ens(bool passB, const SpecArgs &a, const SpecEns &e, int nmembers, hipStream_t s) {
+    const size_t lds = sizeof(double2) * (size_t)FftPlan<N, Geo<N>::T>::LDS;
+    const dim3 grid((unsigned)a.Nc, (unsigned)nmembers);
+    if (passB) {
+        QG_HIP(hipFuncSetAttribute((const void *)spec_passB<N, double, SpecEns>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        spec_passB<N, double><<<grid, Geo<N>::T, lds, s>>>(a, e);
+    } else {
+        QG_HIP(hipFuncSetAttribute((const void *)spec_passA<N, double, SpecEns>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        spec_passA<N, double><<<grid, Geo<N>::T, lds, s>>>(a, e);
+    }
+    QG_LAUNCH_CHECK();
+    return QG_OK;
+}
+
+static int dispatch_pass_ens(bool passB, const SpecArgs &a, const SpecEns &e, int nmembers, hipStream_t s) {
+    switch (a.M) {
+        case 8: return launch_pass_ens<8>(passB, a, e, nmembers, s);
+        case 16: return launch_pass_ens<16>(passB, a, e, nmembers, s);
+        case 32: return launch_pass_ens<32>(passB, a, e, nmembers, s);
+        case 64: return launch_pass_ens<64>(passB, a, e, nmembers, s);
+        case 128: return launch_pass_ens<128>(passB, a, e, nmembers, s);
+        case 256: return launch_pass_ens<256>(passB, a, e, nmembers, s);
+        case 512: return launch_pass_ens<512>(passB, a, e, nmembers, s);
+        case 1024: return launch_pass_ens<1024>(passB, a, e, nmembers, s);
+        case 2048: return launch_pass_ens<2048>(passB, a, e, nmembers, s);
+        default: return QG_ERR_UNSUPPORTED;
+    }
+}
+
 static int dispatch_pass(bool passB, const SpecArgs &a, hipStream_t s) {
     switch (a.M) {
         case 8: return launch_pass<8>(passB, a, s);
@@ -2665,8 +2743,9 @@ static size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
 int SpectralSolver::init(int64_t M, int64_t P, int64_t P_total, int rank, int nranks, double dx,
                          const double alpha[2], int pinned0, const double pin_in[4], const double pin_out[4],
-                         int chunk_rows, int f32) {
+                         int chunk_rows, int f32, int nmembers) {
     if (!supports(M, P)) return QG_ERR_UNSUPPORTED;
+    if (nmembers < 1 || (nmembers > 1 && !supports_members(M, P, nranks, f32))) return QG_ERR_UNSUPPORTED;
     if (!(dx > 0) || nranks < 1 || rank < 0 || rank >= nranks || P_total != P * nranks) return QG_ERR_INVALID_ARG;
     // two points in a direction (global): the reference's laplacian_1d_periodic
     // (laplacian.jl:40-45) writes its wrap entry over the neighbour entry, so its matrix is not
@@ -2779,8 +2858,12 @@ int SpectralSolver::init(int64_t M, int64_t P, int64_t P_total, int rank, int nr
     const size_t n_bl = blue ? align_up(sizeof(double2) * M) + 2 * align_up(sizeof(double2) * BL) +
                                    2 * align_up(sizeof(double2) * (size_t)BL * brows)
                              : 0;
-    bytes_ = n_tw + n_coef + n_hot + n_U + 4 * n_S + n_dc + n_rec + n_grec + n_ext + 2 * n_line + n_scal + n_pinpart +
-             n_tw2 + n_half + n_perm + n_bl;
+    // an ensemble's members 1 .. nmembers-1: a copy each of the block U .. pinpart, behind member 0's
+    const size_t n_member = n_U + 4 * n_S + n_dc + n_rec + n_grec + n_ext + 2 * n_line + n_scal + n_pinpart;
+    const size_t n_more = (size_t)(nmembers - 1) * n_member;
+    nmembers_ = nmembers;
+    member_bytes_ = n_member;
+    bytes_ = n_tw + n_coef + n_hot + n_member + n_more + n_tw2 + n_half + n_perm + n_bl;
     if (hipMalloc(&mem_, bytes_) != hipSuccess) {
         mem_ = nullptr;
         return QG_ERR_ALLOC;
@@ -2805,6 +2888,7 @@ int SpectralSolver::init(int64_t M, int64_t P, int64_t P_total, int rank, int nr
     a.hline = (double *)take(n_line);
     a.scal = (double *)take(n_scal);
     a.pinpart = (double *)take(n_pinpart);
+    char *more = take(n_more);
     a.tw2 = (wide || wsplit) ? (const double2 *)take(n_tw2) : nullptr;
     a.half_tmp = wide ? (void *)take(n_half) : nullptr;
     a.perm = nullptr;
@@ -2883,6 +2967,7 @@ int SpectralSolver::init(int64_t M, int64_t P, int64_t P_total, int rank, int nr
     QG_HIP(hipMemset(a.scal, 0, n_scal));
     QG_HIP(hipMemset(a.line, 0, n_line));
     QG_HIP(hipMemset(a.pinpart, 0, n_pinpart));
+    if (n_more) QG_HIP(hipMemset(more, 0, n_more));  // (the same zeros, and the rest, per member)
     return QG_OK;
 }
 
@@ -2944,6 +3029,21 @@ SpectralSolver::~SpectralSolver() {
     if (mem_) (void)hipFree(mem_);
 }
 
+// The carry launch: k-blocks plus the extra column, and the kernel variant (spec_carry<4>, two
+// workgroups per CU, when one per CU would leave a second round).  Decided from the row length
+// and the device alone -- the single solve and an ensemble's share it, so their bits agree.
+static int carry_geometry(const SpecArgs &a, unsigned *nkb, bool *two_per_cu) {
+    static int cus = 0;
+    if (cus == 0) {
+        int dev = 0;
+        QG_HIP(hipGetDevice(&dev));
+        QG_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    }
+    *nkb = (unsigned)((a.KH + CARRY_KB - 1) / CARRY_KB) + 1;
+    *two_per_cu = 2 * (int)*nkb > cus;
+    return QG_OK;
+}
+
 int SpectralSolver::solve(const void *in1, const void *in2, void *out1, void *out2, int write_ghost_rows,
                           hipStream_t s, GatherFn gather, void *user, const double *pin_in, const double *pin_out,
                           void *zcopy1, void *zcopy2) {
@@ -2973,14 +3073,10 @@ int SpectralSolver::solve(const void *in1, const void *in2, void *out1, void *ou
     a.npin = a.fuse_pin ? (a.KH + CARRY_KB - 1) / CARRY_KB : pin_kblocks(a.KH);
     QG_CHECK(dispatch_pass(false, a, s));
     {
-        const unsigned nkb = (unsigned)((a.KH + CARRY_KB - 1) / CARRY_KB) + 1;
-        static int cus = 0;
-        if (cus == 0) {
-            int dev = 0;
-            QG_HIP(hipGetDevice(&dev));
-            QG_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        }
-        if (2 * (int)nkb > cus) spec_carry<4><<<dim3(nkb, 2), 64 * CARRY_WAVES, 0, s>>>(a);
+        unsigned nkb = 0;
+        bool two_per_cu = false;
+        QG_CHECK(carry_geometry(a, &nkb, &two_per_cu));
+        if (two_per_cu) spec_carry<4><<<dim3(nkb, 2), 64 * CARRY_WAVES, 0, s>>>(a);
         else spec_carry<1><<<dim3(nkb, 2), 64 * CARRY_WAVES, 0, s>>>(a);
     }
     QG_LAUNCH_CHECK();
@@ -2993,6 +3089,41 @@ int SpectralSolver::solve(const void *in1, const void *in2, void *out1, void *ou
         QG_LAUNCH_CHECK();
     }
     QG_CHECK(dispatch_pass(true, a, s));
+    return QG_OK;
+}
+
+bool SpectralSolver::supports_members(int64_t M, int64_t P, int nranks, int f32) {
+    return nranks == 1 && !f32 && P >= 3 && M >= 8 && M <= 2048 && (M & (M - 1)) == 0;
+}
+
+// The solve of every member of an ensemble: the launches of solve() on one rank (pass A, the
+// carry with the fused pin, pass B), each over all members.  The carry variant is chosen as
+// solve() chooses it, from (M, P) alone.
+int SpectralSolver::solve_members(const void *in1, const void *in2, void *out1, void *out2, int64_t field_stride_bytes,
+                                  hipStream_t s) {
+    if (!mem_) return QG_ERR_NOT_BOUND;
+    if (a_.two || !supports_members(a_.M, a_.P, a_.nranks, a_.f32)) return QG_ERR_UNSUPPORTED;
+    SpecArgs a = a_;
+    a.zcopy1 = a.zcopy2 = nullptr;
+    a.in1 = in1;
+    a.in2 = in2;
+    a.out1 = out1;
+    a.out2 = out2;
+    a.write_ghost_rows = 1;
+    a.fuse_pin = 1;
+    a.npin = (a.KH + CARRY_KB - 1) / CARRY_KB;
+    const SpecEns e{(int64_t)member_bytes_, field_stride_bytes};
+    QG_CHECK(dispatch_pass_ens(false, a, e, nmembers_, s));
+    {
+        unsigned nkb = 0;
+        bool two_per_cu = false;
+        QG_CHECK(carry_geometry(a, &nkb, &two_per_cu));
+        const dim3 grid(nkb, 2, (unsigned)nmembers_);
+        if (two_per_cu) spec_carry<4><<<grid, 64 * CARRY_WAVES, 0, s>>>(a, e);
+        else spec_carry<1><<<grid, 64 * CARRY_WAVES, 0, s>>>(a, e);
+    }
+    QG_LAUNCH_CHECK();
+    QG_CHECK(dispatch_pass_ens(true, a, e, nmembers_, s));
     return QG_OK;
 }
 

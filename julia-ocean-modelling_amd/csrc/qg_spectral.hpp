@@ -113,7 +113,8 @@ class SpectralSolver {
 public:
     // alpha[s]: construct_spA shift; pinned0: system 0 is the pinned Poisson problem
     int init(int64_t M, int64_t P, int64_t P_total, int rank, int nranks, double dx, const double alpha[2],
-             int pinned0, const double pin_in[4], const double pin_out[4], int chunk_rows, int f32 = 0);
+             int pinned0, const double pin_in[4], const double pin_out[4], int chunk_rows, int f32 = 0,
+             int nmembers = 1);  // nmembers > 1: an ensemble's solver (supports_members, solve_members)
     ~SpectralSolver();
     static bool supports(int64_t M, int64_t P);
     // enqueue the whole solve; `gather` (may be null) all-gathers rec -> grec across ranks
@@ -122,6 +123,13 @@ public:
               hipStream_t s, GatherFn gather = nullptr, void *user = nullptr, const double *pin_in = nullptr,
               const double *pin_out = nullptr,  // optional per-call projections
               void *zcopy1 = nullptr, void *zcopy2 = nullptr);  // see SpecArgs::zcopy1
+    // Ensembles: nmembers solves per launch, member b's fields field_stride_bytes * b behind the
+    // given ones (in1 .. out2: member 0's), every member with its own scratch and the shared
+    // tables.  Same chunking and per-point arithmetic as solve(): bit-identical per member.
+    static bool supports_members(int64_t M, int64_t P, int nranks, int f32);
+    int solve_members(const void *in1, const void *in2, void *out1, void *out2, int64_t field_stride_bytes,
+                      hipStream_t s);
+    int members() const { return nmembers_; }
     // pass A can write the zcopy fields (power-of-two rows: the FFT and wide-row passes)
     bool fuses_input_copy() const { return !a_.two && a_.M >= 8 && a_.M <= 8192 && (a_.M & (a_.M - 1)) == 0; }
     const SpecArgs &args() const { return a_; }
@@ -135,6 +143,8 @@ private:
     void *mem_ = nullptr;
     double *grec_buf_ = nullptr;
     size_t bytes_ = 0;
+    int nmembers_ = 1;         // scratch blocks (U .. pinpart) allocated
+    size_t member_bytes_ = 0;  // bytes of one
 };
 
 }  // namespace qg

@@ -962,13 +962,14 @@ int launch_fill_ghost_cols(double *b, int64_t M, int64_t P, hipStream_t s) {
 // kernels are bit-identical.  Block: 64 x-points (one wave) x 4 rows.
 // ------------------------------------------------------------------------------------
 // one point (i, j) of one layer: loads, tendency, AB3 update, stores; returns the centre
-// values the certification uses (zeta, lap(psi), psi)
+// values the certification uses (zeta, lap(psi), psi).  off: elements added to every field
+// pointer of `a` (an ensemble member's block; 0 for a single context)
 template <class T>
 __device__ __forceinline__ void direct_point(const TendArgsT<T> &a, int layer, int i, int j, T &zc_out, T &L0_out,
-                                             T &P0_out) {
+                                             T &P0_out, const size_t off = 0) {
     const int M = (int)a.M, P = (int)a.P;
     const int64_t ld = a.ld;
-    const T *psi = a.psi[layer], *zeta = a.zeta[layer];
+    const T *psi = a.psi[layer] + off, *zeta = a.zeta[layer] + off;
     const RowSrcT<T> &prs = a.psi_rows[layer];
     const RowSrcT<T> &zrs = a.zeta_rows[layer];
     const T dx = (T)a.dx, idx = T(1) / dx, idx2 = idx * idx;
@@ -982,7 +983,7 @@ __device__ __forceinline__ void direct_point(const TendArgsT<T> &a, int layer, i
     };
     auto rowp = [&](const T *base, const RowSrcT<T> &rs, int jj) -> const T * {
         if (jj >= 0 && jj < P) return base + fidx(1, jj + 1, ld);
-        return rs.halo[jj < 0 ? jj + 2 : (jj - P) + 2];
+        return rs.halo[jj < 0 ? jj + 2 : (jj - P) + 2] + off;
     };
     const T *pr[5], *zr[3];
 #pragma unroll
@@ -1011,18 +1012,18 @@ __device__ __forceinline__ void direct_point(const TendArgsT<T> &a, int layer, i
     T zn, f1c = 0, f2c = 0;
     if (a.ab3) {
         const size_t o = (size_t)(j + 1) * ld + i + 1;
-        f1c = ld_stream(a.fprev1[layer] + o);
-        f2c = ld_stream(a.fprev2[layer] + o);
+        f1c = ld_stream(a.fprev1[layer] + off + o);
+        f2c = ld_stream(a.fprev2[layer] + off + o);
         zn = zcen + dtT * ((((T)(23.0 / 12.0) * F) - ((T)(16.0 / 12.0) * f1c)) + ((T)(5.0 / 12.0) * f2c));
     } else {
         zn = zcen + (dtT * F);
     }
-    T *zo = a.zeta_out[layer], *fo = a.f_out[layer];
+    T *zo = a.zeta_out[layer] + off, *fo = a.f_out[layer] + off;
     const bool gr = a.write_ghost_rows;
     store_row_with_ghosts(zo + (size_t)(j + 1) * ld, ghost_row_target(zo, ld, P, j, gr), M, i, zn);
     store_row_with_ghosts(fo + (size_t)(j + 1) * ld, ghost_row_target(fo, ld, P, j, gr), M, i, F);
     if (a.ab3 && a.fshift1[layer]) {  // (see TendArgsT::fshift1)
-        T *s1 = a.fshift1[layer], *s2 = a.fshift2[layer];
+        T *s1 = a.fshift1[layer] + off, *s2 = a.fshift2[layer] + off;
         store_row_with_ghosts(s1 + (size_t)(j + 1) * ld, ghost_row_target(s1, ld, P, j, gr), M, i, f1c);
         store_row_with_ghosts(s2 + (size_t)(j + 1) * ld, ghost_row_target(s2, ld, P, j, gr), M, i, f2c);
     }
@@ -1045,6 +1046,26 @@ __global__ __launch_bounds__(256) void tendency_direct_kernel(TendArgsT<T> a, in
     if (i >= M || j >= r1) return;  // no barriers below
     T zc, L0, P0;
     direct_point(a, layer, i, j, zc, L0, P0);
+}
+
+// Ensembles (qg_mi355_ensemble.h): the same point for every member of a batch in one launch.
+// The grid is linear -- (strips of 64) x (blocks of 4 rows) x layer x member workgroups, member
+// slowest, decoded from the XCD-aware logical id as tend_block() does -- so no factor has to fit
+// a grid's 65 535-wide y or z extent.  Member b's fields lie b * mstride elements behind member
+// 0's (direct_point's off); everything else (parameters, wind table) is shared.
+__global__ __launch_bounds__(256) void tendency_direct_ens_kernel(TendArgsT<double> a, int nx, int ny, int64_t mstride) {
+    const int b = xcd_logical_id();
+    const int x = b % nx;
+    int r = b / nx;
+    const int y = r % ny;
+    r /= ny;
+    const int layer = r & 1;
+    const size_t off = (size_t)(r >> 1) * (size_t)mstride;
+    const int i = x * 64 + (int)(threadIdx.x & 63);
+    const int j = a.j0 + 4 * y + (int)(threadIdx.x >> 6);
+    if (i >= (int)a.M || j >= a.j1) return;  // no barriers below
+    double zc, L0, P0;
+    direct_point(a, layer, i, j, zc, L0, P0, off);
 }
 
 // The certifying form of the cache-resident kernel (PCG, one rank, small grids): each thread
@@ -1256,6 +1277,17 @@ static int launch_tend_direct(const TendArgsT<T> &a, hipStream_t s) {
     const int nA = (a.j1 - a.j0 + 3) / 4, nB = a.j3 > a.j2 ? (a.j3 - a.j2 + 3) / 4 : 0;
     dim3 grid((unsigned)((a.M + 63) / 64), (unsigned)(nA + nB), 2);
     tendency_direct_kernel<T><<<grid, 256, 0, s>>>(a, nA, nB);
+    QG_LAUNCH_CHECK();
+    return QG_OK;
+}
+
+// the one-point tendency of rows [j0, j1) for nmembers members (one rank, F64; see the kernel)
+int launch_tendency_members(const TendArgsT<double> &a, int nmembers, int64_t member_stride, hipStream_t s) {
+    if (nmembers < 1 || a.j1 <= a.j0 || a.j3 > a.j2) return QG_ERR_INVALID_ARG;
+    const int nx = (int)((a.M + 63) / 64), ny = (a.j1 - a.j0 + 3) / 4;
+    const int64_t blocks = (int64_t)nx * ny * 2 * nmembers;
+    if (blocks > 0x7fffffff) return QG_ERR_UNSUPPORTED;
+    tendency_direct_ens_kernel<<<(unsigned)blocks, 256, 0, s>>>(a, nx, ny, member_stride);
     QG_LAUNCH_CHECK();
     return QG_OK;
 }

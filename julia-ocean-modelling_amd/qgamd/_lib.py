@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("QGMI355_LIB") or os.path.join(PKG_DIR, "lib", "libqgm
 QG_OK = 0
 QG_ERR_INVALID_ARG, QG_ERR_UNSUPPORTED, QG_ERR_HIP, QG_ERR_NOT_BOUND = -1, -2, -3, -4
 QG_ERR_ALLOC, QG_ERR_RCCL, QG_ERR_NOT_CONVERGED = -5, -6, -7
+QG_ENS_MAX_MEMBERS = 65535
 QG_XBUF_TO_NEXT, QG_XBUF_TO_PREV, QG_XBUF_FROM_PREV, QG_XBUF_FROM_NEXT = 0, 1, 2, 3
 QG_SOLVER_SPECTRAL = 0
 QG_F64, QG_F32 = 0, 1
@@ -63,7 +64,7 @@ SendrecvFn = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.
                          C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
                          C.POINTER(C.c_int), C.c_void_p)
 
-# (name, restype, argtypes) of every symbol include/qg_mi355.h declares
+# (name, restype, argtypes) of every symbol include/qg_mi355.h and qg_mi355_ensemble.h declare
 _vp, _dp, _i64, _i32 = C.c_void_p, C.c_void_p, C.c_int64, C.c_int
 SIGNATURES = [
     ("qg_abi_version", C.c_int, []),
@@ -111,6 +112,18 @@ SIGNATURES = [
     ("qg_cd", C.c_int, [_dp, _dp, _i64, _i64, C.c_double, _vp]),
     ("qg_arakawa_J", C.c_int, [_dp, _dp, _dp, _i64, _i64, C.c_double, _vp]),
     ("qg_fill_ghosts", C.c_int, [_dp, _i64, _i64, _vp]),
+    # include/qg_mi355_ensemble.h
+    ("qg_ens_create", C.c_int, [C.POINTER(QgParams), C.c_int, C.c_int, _vp, C.POINTER(_vp)]),
+    ("qg_ens_destroy", C.c_int, [_vp]),
+    ("qg_ens_members", C.c_int, [_vp, C.POINTER(C.c_int)]),
+    ("qg_ens_bind_state", C.c_int, [_vp, _dp, _dp, _dp]),
+    ("qg_ens_initialise", C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("qg_ens_step", C.c_int, [_vp, _i64]),
+    ("qg_ens_run", C.c_int, [_vp, _i64, _i64]),
+    ("qg_ens_slot", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    ("qg_ens_canonicalize", C.c_int, [_vp]),
+    ("qg_ens_diagnostics", C.c_int, [_vp, C.POINTER(QgDiag)]),
+    ("qg_ens_synchronize", C.c_int, [_vp]),
 ]
 
 _lib = None

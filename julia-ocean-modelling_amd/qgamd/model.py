@@ -547,6 +547,123 @@ def run_model_no_output(m, nsteps=None, seeds=(SEED_LAYER1, SEED_LAYER2), **kw):
     return st
 
 
+# ---------------------------------------------------------------------------------------
+# batched ensembles (include/qg_mi355_ensemble.h)
+# ---------------------------------------------------------------------------------------
+def ensemble_seeds(nmembers):
+    """The default seeds of an ensemble: member b gets (SEED_LAYER1 + 2b, SEED_LAYER2 + 2b), so
+    member 0 is the default single run and no two layers of any members share a seed."""
+    return [(SEED_LAYER1 + 2 * b, SEED_LAYER2 + 2 * b) for b in range(int(nmembers))]
+
+
+class Ensemble:
+    """B members of one model -- same parameters, different states -- advanced together: every
+    step is the four kernel launches a :class:`State` needs for one member (qg_ens_*).
+
+    ``zeta``, ``psi``, ``f_store`` are (B, 3, 2, P+2, M+2) float64 tensors (the Julia
+    (M+2, P+2, 2, 3, B) arrays); member b's block is a :class:`State`'s array, and after the same
+    calls holds bit for bit what a State with that member's seeds holds.  The history slots
+    rotate with one set of heads for all members.  F64, spectral solver, one GPU, M a power of
+    two in 8..2048, P >= 3 (QGError with QG_ERR_UNSUPPORTED otherwise)."""
+
+    def __init__(self, m, nmembers, seeds=None, chunk_rows=0, P_fwd=None, wind=None, device=None):
+        """seeds: a sequence of B (seed1, seed2) pairs to initialise with right away, or None
+        (call :meth:`initialise`, or fill the tensors, before stepping)."""
+        _lib.lib()  # the HIP library first: no CPU fallback, fail before touching the device
+        torch = _torch()
+        self.model = m
+        self.nmembers = int(nmembers)
+        self.params = qg_params(m, _lib.QG_SOLVER_SPECTRAL, P_fwd, chunk_rows, wind=wind)
+        self._ens = C.c_void_p()
+        if device is None:
+            self.device = torch.cuda.current_device()
+        else:
+            dev = torch.device(device) if not isinstance(device, int) else torch.device("cuda", device)
+            if dev.type != "cuda":
+                raise ValueError(f"Ensemble needs a CUDA (HIP) device, got {dev}")
+            self.device = dev.index if dev.index is not None else torch.cuda.current_device()
+        with torch.cuda.device(self.device):
+            # created first: an unsupported configuration is refused before anything is allocated
+            call("qg_ens_create", C.byref(self.params), self.nmembers, int(self.device), _stream_ptr(),
+                 C.byref(self._ens))
+            shape = (self.nmembers, 3, 2, m.P + 2, m.M + 2)
+            dev = torch.device("cuda", self.device)
+            self.zeta = torch.zeros(shape, dtype=torch.float64, device=dev)
+            self.psi = torch.zeros(shape, dtype=torch.float64, device=dev)
+            self.f_store = torch.zeros(shape, dtype=torch.float64, device=dev)
+            call("qg_ens_bind_state", self._ens, _ptr(self.zeta), _ptr(self.psi), _ptr(self.f_store))
+            if seeds is not None:
+                self.initialise(seeds)
+
+    def close(self):
+        """Destroy the library handle now (qg_ens_destroy); the tensors stay with the caller."""
+        ens = getattr(self, "_ens", None)
+        if ens and _lib._lib is not None:
+            _lib._lib.qg_ens_destroy(ens)
+            self._ens = None
+
+    def __del__(self):
+        self.close()
+
+    def member(self, b):
+        """The (zeta, psi, f_store) views of member b, each (3, 2, P+2, M+2)."""
+        return self.zeta[b], self.psi[b], self.f_store[b]
+
+    def initialise(self, seeds=None):
+        """qg_ens_initialise: initialise_model per member from B (seed1, seed2) pairs (default
+        :func:`ensemble_seeds`)."""
+        seeds = ensemble_seeds(self.nmembers) if seeds is None else list(seeds)
+        if len(seeds) != self.nmembers:
+            raise ValueError(f"{len(seeds)} seed pairs for {self.nmembers} members")
+        arr = C.c_uint64 * self.nmembers
+        call("qg_ens_initialise", self._ens, arr(*[int(s[0]) for s in seeds]), arr(*[int(s[1]) for s in seeds]))
+        return self
+
+    def step(self, timestep):
+        call("qg_ens_step", self._ens, int(timestep))
+
+    def run(self, first_step, nsteps):
+        call("qg_ens_run", self._ens, int(first_step), int(nsteps))
+
+    def synchronize(self):
+        call("qg_ens_synchronize", self._ens)
+
+    def slot(self, which, logical):
+        w = {"zeta": 0, "psi": 1, "f_store": 2}[which]
+        out = C.c_int()
+        call("qg_ens_slot", self._ens, w, int(logical), C.byref(out))
+        return out.value
+
+    def logical(self, which):
+        """(B, 3, 2, P+2, M+2) tensor in reference slot order (a gathered copy)."""
+        torch = _torch()
+        t = getattr(self, which)
+        order = [self.slot(which, s) for s in (1, 2, 3)]
+        return t[:, torch.tensor(order, device=t.device)]
+
+    def current(self, which, layer):
+        """Reference ``X[:, :, layer, 1]`` (layer 1-based) of every member: a (B, P+2, M+2) view."""
+        return getattr(self, which)[:, self.slot(which, 1), layer - 1]
+
+    def canonicalize(self):
+        call("qg_ens_canonicalize", self._ens)
+
+    def diagnostics(self):
+        """qg_ens_diagnostics: a list of B dicts shaped like :meth:`State.diagnostics`."""
+        d = (_lib.QgDiag * self.nmembers)()
+        call("qg_ens_diagnostics", self._ens, d)
+        return [{f: (list(getattr(r, f)) if f != "interface" else r.interface)
+                 for f, _ in _lib.QgDiag._fields_ if f != "reserved"} for r in d]
+
+
+def run_ensemble_no_output(m, nmembers, nsteps=None, seeds=None, **kw):
+    """run_model_no_output for B members at once: init, floor(T/dt) steps; returns the Ensemble."""
+    ens = Ensemble(m, nmembers, **kw).initialise(seeds)
+    total = int(np.floor(m.T / m.dt)) if nsteps is None else int(nsteps)
+    ens.run(1, total)
+    return ens
+
+
 # ---- stateless operators on (P+2, M+2) device matrices -----------------------------------
 def _dims(u):
     P2, M2 = u.shape[-2:]
