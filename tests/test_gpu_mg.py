@@ -99,7 +99,9 @@ def test_mg_at_baseline_size(env, N):
 @pytest.mark.parametrize("G,N", [(2, 256), (4, 256)])
 def test_mg_slabs_match_single_gpu(env, G, N):
     """G y-slabs over the in-process transport: PCG's operator, dots and p halos cross the
-    slabs; each rank's V-cycle is its own slab's (block Jacobi).  Same answer as one GPU."""
+    slabs, and the V-cycle is the one global cycle (slab levels read their y neighbours from
+    refreshed ghost rows; the coarse levels are all-gathered and cycled identically on every
+    rank, qg_mg.hip).  Same answer as one GPU."""
     torch, qg, R, O, ThreadRing = env
     m = qg.bench_model(N)
     steps = 4

@@ -2,9 +2,12 @@
 default) against the one-point kernel it replaces (`tendency_kernel`, selected with
 qg_set_form(QG_FORM_TENDENCY, QG_TEND_ONE_POINT)): the same arithmetic in the same order per
 point, so every field must be bit-identical after several Euler + AB3 steps.  Grids above the
-direct kernel's cut-off (1.2 M points per layer) so the LDS-ring kernels run; M = 1500 leaves a
-partial last strip (F32 states need even M), the rows of whole strips run the 5-per-CU kernel,
-M = 1024 / 512 with every strip (one) an edge strip."""
+direct kernel's cut-off (1.2 M points per layer) so the LDS-ring kernels run.  The pair
+kernel's strips are 512 points wide, interior when 2 <= x0 and x0 + 514 <= M: M = 2048 has two
+interior strips between two edge strips; M = 1500 one interior strip and a partial last strip
+of 476 columns (F32 states need even M); M = 1024 two edge strips; M = 512 one strip with the
+modulo wrap.  The smallest shapes that reach each pair strip body are in
+test_gpu_tendency_geometry.py."""
 import os
 import sys
 
