@@ -245,6 +245,18 @@ int launch_tendency(const TendArgsT<float> &a, hipStream_t s);
 // ensembles: rows [j0, j1) of nmembers members in one launch of the cache-resident one-point
 // form; member b's fields lie b * member_stride elements behind the pointers of `a`
 int launch_tendency_members(const TendArgsT<double> &a, int nmembers, int64_t member_stride, hipStream_t s);
+// perturbed-parameter ensembles: one member's tendency parameters (a 64-byte record of a device
+// table; the sweep kernel reads them per workgroup in place of TendArgsT's)
+struct alignas(64) TendMember {
+    double visc, U, r;
+    double beta[2];
+    const double *wind;  // [P] wind forcing of this member's rows, or nullptr (no wind)
+    double pad[2];
+};
+static_assert(sizeof(TendMember) == 64, "one record per 64-byte line");
+// launch_tendency_members with member b's (visc, U, r, beta, wind) taken from rec[b] (device)
+int launch_tendency_sweep(const TendArgsT<double> &a, int nmembers, int64_t member_stride, const TendMember *rec,
+                          hipStream_t s);
 // the same tendency, both layers per workgroup, also certifying the previous solve (a.cert):
 // *nblk = workgroups launched (partials written); a grid of more than `cap` workgroups (the
 // partials' capacity) is refused before anything is launched

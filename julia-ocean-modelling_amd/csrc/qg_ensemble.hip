@@ -9,6 +9,14 @@
 // Shared: parameters, the wind table, the solver's twiddles and coefficient tables.  Per member:
 // the state and the solver's scratch.  Per-point arithmetic and chunking are a single
 // context's, so every member's bits are a single context's.
+//
+// Perturbed-parameter ensembles (include/qg_mi355_sweep.h): members may carry their own
+// (U, beta, r, visc, R_d, initial_kick, wind_tau0).  Decided once at creation:
+//   every member's tendency record equal    the launches above, on member 0's values
+//   records differ, every R_d equal         launch_tendency_sweep + solve_members
+//   R_d differs                             launch_tendency_sweep + solve_members on per-member
+//                                           tables (SpectralSolver::init_member_tables)
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <new>
@@ -16,6 +24,7 @@
 
 #include "qg_common.hpp"
 #include "qg_mi355_ensemble.h"
+#include "qg_mi355_sweep.h"
 #include "qg_spectral.hpp"
 
 namespace qg {
@@ -35,7 +44,11 @@ struct qg_ens {
     int nmembers = 0;
     double *zeta = nullptr, *psi = nullptr, *fst = nullptr;
     int heads[3] = {0, 0, 0};  // physical slot of logical slot 1 for zeta, psi, f_store (all members)
-    double *wind = nullptr;    // [P] wind forcing of the rows (qg_params.wind_tau0 != 0)
+    double *wind = nullptr;    // [P] wind forcing of the rows (members' wind_tau0 != 0), one table
+                               // per member with wind when the members differ
+    std::vector<qg_member_params> mp;  // the members' own parameters (qg_mi355_sweep.h)
+    std::vector<Derived> md;           // derive() of the base with member b's values substituted
+    TendMember *rec = nullptr;         // device [nmembers] records: the sweep tendency (else null)
     double *diag = nullptr;    // diagnostics: partial records (reused member after member) | nmembers records
     SpectralSolver spec;
     size_t F = 0;  // doubles per (M+2, P+2) field
@@ -44,34 +57,114 @@ struct qg_ens {
     double *field(double *base, int layer, int slot) const { return base + F * (size_t)(layer + 2 * slot); }
 };
 
-extern "C" {
+// the base parameters with member m's seven values substituted
+static qg_params member_qg_params(const qg_params &p, const qg_member_params &m) {
+    qg_params q = p;
+    q.U = m.U;
+    q.beta = m.beta;
+    q.r = m.r;
+    q.visc = m.visc;
+    q.R_d = m.R_d;
+    q.initial_kick = m.initial_kick;
+    q.wind_tau0 = m.wind_tau0;
+    return q;
+}
 
-int qg_ens_create(const qg_params *p, int nmembers, int device, void *stream, qg_ens **out) {
-    if (!out) return QG_ERR_INVALID_ARG;
-    *out = nullptr;
-    if (nmembers < 1 || nmembers > QG_ENS_MAX_MEMBERS) return QG_ERR_INVALID_ARG;
+static qg_member_params base_member_params(const qg_params &p) {
+    qg_member_params m;
+    m.U = p.U;
+    m.beta = p.beta;
+    m.r = p.r;
+    m.visc = p.visc;
+    m.R_d = p.R_d;
+    m.initial_kick = p.initial_kick;
+    m.wind_tau0 = p.wind_tau0;
+    m.reserved = 0.0;
+    return m;
+}
+
+static bool same_bits(double a, double b) { return std::memcmp(&a, &b, sizeof(double)) == 0; }
+
+// mp: nmembers records, or null for the base's values in every member (qg_ens_create)
+static int ens_create(const qg_params *p, const qg_member_params *mp, int nmembers, int device, void *stream,
+                      qg_ens **out) {
     QG_CHECK(check_create_params(p));
     if (p->dtype != QG_F64 || p->solver != QG_SOLVER_SPECTRAL) return QG_ERR_UNSUPPORTED;
     if (!SpectralSolver::supports_members(p->M, p->P, 1, 0)) return QG_ERR_UNSUPPORTED;
+    if (mp)
+        for (int b = 0; b < nmembers; ++b) {
+            const qg_member_params &m = mp[b];
+            for (double v : {m.U, m.beta, m.r, m.visc, m.R_d, m.initial_kick, m.wind_tau0})
+                if (!std::isfinite(v)) return QG_ERR_INVALID_ARG;
+            if (!same_bits(m.reserved, 0.0)) return QG_ERR_INVALID_ARG;
+            const qg_params q = member_qg_params(*p, m);
+            QG_CHECK(check_create_params(&q));
+        }
     qg_ens *e = new (std::nothrow) qg_ens();
     if (!e) return QG_ERR_ALLOC;
     e->p = *p;
-    e->d = derive(*p);
     e->device = device;
     e->stream = static_cast<hipStream_t>(stream);
     e->nmembers = nmembers;
     e->F = (size_t)(p->M + 2) * (size_t)(p->P + 2);
+    e->mp.assign((size_t)nmembers, base_member_params(*p));
+    if (mp) std::memcpy(e->mp.data(), mp, sizeof(qg_member_params) * (size_t)nmembers);
+    e->md.resize((size_t)nmembers);
+    for (int b = 0; b < nmembers; ++b) e->md[b] = derive(member_qg_params(*p, e->mp[b]));
+    e->d = e->md[0];
+    // which kernels (see the head of this file): compared bit for bit
+    bool tend_differs = false, rd_differs = false;
+    for (int b = 1; b < nmembers; ++b) {
+        const qg_member_params &m = e->mp[b], &m0 = e->mp[0];
+        const Derived &d = e->md[b], &d0 = e->md[0];
+        if (!same_bits(m.visc, m0.visc) || !same_bits(m.U, m0.U) || !same_bits(m.r, m0.r) ||
+            !same_bits(d.beta1, d0.beta1) || !same_bits(d.beta2, d0.beta2) || !same_bits(m.wind_tau0, m0.wind_tau0))
+            tend_differs = true;
+        if (!same_bits(m.R_d, m0.R_d)) rd_differs = true;
+    }
+    if (rd_differs) tend_differs = true;  // (the table's third row: the sweep tendency with the sweep solver)
     auto build = [&]() -> int {
         QG_HIP(hipSetDevice(device));
-        if (p->wind_tau0 != 0) {
-            std::vector<double> w((size_t)p->P);
-            for (int64_t j = 0; j < p->P; ++j) w[j] = wind_row(p->wind_tau0, p->wind_rho0, p->H_1, p->dx, p->P, j);
-            if (hipMalloc((void **)&e->wind, sizeof(double) * p->P) != hipSuccess) return QG_ERR_ALLOC;
-            QG_HIP(hipMemcpy(e->wind, w.data(), sizeof(double) * p->P, hipMemcpyHostToDevice));
+        const int64_t P = p->P;
+        // one [P] wind table per member with wind (one for all when the members are equal)
+        std::vector<int64_t> wslot((size_t)nmembers, -1);
+        int64_t nw = 0;
+        for (int b = 0; b < (tend_differs ? nmembers : 1); ++b)
+            if (e->mp[b].wind_tau0 != 0) wslot[b] = nw++;
+        if (nw) {
+            std::vector<double> w((size_t)(nw * P));
+            for (int b = 0; b < nmembers; ++b)
+                for (int64_t j = 0; wslot[b] >= 0 && j < P; ++j)
+                    w[wslot[b] * P + j] = wind_row(e->mp[b].wind_tau0, p->wind_rho0, p->H_1, p->dx, P, j);
+            if (hipMalloc((void **)&e->wind, sizeof(double) * w.size()) != hipSuccess) return QG_ERR_ALLOC;
+            QG_HIP(hipMemcpy(e->wind, w.data(), sizeof(double) * w.size(), hipMemcpyHostToDevice));
+        }
+        if (tend_differs) {
+            std::vector<TendMember> rec((size_t)nmembers);
+            for (int b = 0; b < nmembers; ++b) {
+                TendMember &t = rec[b];
+                t.visc = e->mp[b].visc;
+                t.U = e->mp[b].U;
+                t.r = e->mp[b].r;
+                t.beta[0] = e->md[b].beta1;
+                t.beta[1] = e->md[b].beta2;
+                t.wind = wslot[b] >= 0 ? e->wind + wslot[b] * P : nullptr;
+                t.pad[0] = t.pad[1] = 0.0;
+            }
+            if (hipMalloc((void **)&e->rec, sizeof(TendMember) * rec.size()) != hipSuccess) return QG_ERR_ALLOC;
+            QG_HIP(hipMemcpy(e->rec, rec.data(), sizeof(TendMember) * rec.size(), hipMemcpyHostToDevice));
         }
         const double alpha[2] = {0.0, e->d.Seig};
         QG_CHECK(e->spec.init(p->M, p->P, p->P, 0, 1, p->dx, alpha, 1, e->d.Pinv, p->P_fwd, p->chunk_rows, 0,
                               nmembers));
+        if (rd_differs) {
+            std::vector<double> alpha1((size_t)nmembers), pin((size_t)nmembers * 4);
+            for (int b = 0; b < nmembers; ++b) {
+                alpha1[b] = e->md[b].Seig;
+                std::memcpy(&pin[4 * (size_t)b], e->md[b].Pinv, sizeof(double) * 4);
+            }
+            QG_CHECK(e->spec.init_member_tables(alpha1.data(), pin.data()));
+        }
         const size_t nd = diag_scratch_doubles() + (size_t)diag_record_len() * nmembers;
         if (hipMalloc((void **)&e->diag, sizeof(double) * nd) != hipSuccess) return QG_ERR_ALLOC;
         return QG_OK;
@@ -85,10 +178,40 @@ int qg_ens_create(const qg_params *p, int nmembers, int device, void *stream, qg
     return QG_OK;
 }
 
+extern "C" {
+
+int qg_ens_create(const qg_params *p, int nmembers, int device, void *stream, qg_ens **out) {
+    if (!out) return QG_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (nmembers < 1 || nmembers > QG_ENS_MAX_MEMBERS) return QG_ERR_INVALID_ARG;
+    return ens_create(p, nullptr, nmembers, device, stream, out);
+}
+
+int qg_ens_create_sweep(const qg_params *p, const qg_member_params *mp, int nmembers, int device, void *stream,
+                        qg_ens **out) {
+    if (!out) return QG_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (nmembers < 1 || nmembers > QG_ENS_MAX_MEMBERS || !mp) return QG_ERR_INVALID_ARG;
+    return ens_create(p, mp, nmembers, device, stream, out);
+}
+
+int qg_member_params_default(const qg_params *p, qg_member_params *out) {
+    if (!p || !out) return QG_ERR_INVALID_ARG;
+    *out = base_member_params(*p);
+    return QG_OK;
+}
+
+int qg_ens_member_params(const qg_ens *e, int b, qg_member_params *out) {
+    if (!e || !out || b < 0 || b >= e->nmembers) return QG_ERR_INVALID_ARG;
+    *out = e->mp[(size_t)b];
+    return QG_OK;
+}
+
 int qg_ens_destroy(qg_ens *e) {
     if (!e) return QG_OK;
     (void)hipSetDevice(e->device);
     if (e->wind) (void)hipFree(e->wind);
+    if (e->rec) (void)hipFree(e->rec);
     if (e->diag) (void)hipFree(e->diag);
     delete e;
     return QG_OK;
@@ -116,11 +239,11 @@ int qg_ens_initialise(qg_ens *e, const uint64_t *seed1, const uint64_t *seed2) {
     if (!e->zeta) return QG_ERR_NOT_BOUND;
     const qg_params &p = e->p;
     QG_HIP(hipSetDevice(e->device));
-    const double amp = p.initial_kick * p.U * p.Ly;
     for (int b = 0; b < e->nmembers; ++b) {
         const size_t o = e->member_stride() * (size_t)b;
+        const double amp = e->mp[b].initial_kick * e->mp[b].U * p.Ly;
         QG_CHECK(launch_initialise_global(e->zeta + o, e->psi + o, e->fst + o, (int)sizeof(double), p.M, p.P, p.P, 0,
-                                          amp, e->d.S1, e->d.S2, p.dx, seed1[b], seed2[b], e->stream));
+                                          amp, e->md[b].S1, e->md[b].S2, p.dx, seed1[b], seed2[b], e->stream));
     }
     e->heads[0] = e->heads[1] = e->heads[2] = 0;
     return QG_OK;
@@ -136,10 +259,10 @@ static int ens_evolve_zeta(qg_ens *e, int64_t timestep) {
     a.P = p.P;
     a.ld = p.M + 2;
     a.dx = p.dx;
-    a.visc = p.visc;
+    a.visc = e->mp[0].visc;  // member 0's: every member's, unless e->rec carries their own
     a.dt = p.dt;
-    a.U = p.U;
-    a.r = p.r;
+    a.U = e->mp[0].U;
+    a.r = e->mp[0].r;
     a.beta[0] = e->d.beta1;
     a.beta[1] = e->d.beta2;
     a.ab3 = timestep >= 3;
@@ -162,7 +285,8 @@ static int ens_evolve_zeta(qg_ens *e, int64_t timestep) {
             a.psi_rows[l].halo[h] = a.psi[l] + fidx(1, rows[h] + 1, ld);
         }
     }
-    QG_CHECK(launch_tendency_members(a, e->nmembers, (int64_t)e->member_stride(), e->stream));
+    if (e->rec) QG_CHECK(launch_tendency_sweep(a, e->nmembers, (int64_t)e->member_stride(), e->rec, e->stream));
+    else QG_CHECK(launch_tendency_members(a, e->nmembers, (int64_t)e->member_stride(), e->stream));
     e->heads[0] = zn;
     e->heads[2] = fn;
     return QG_OK;

@@ -107,6 +107,31 @@ __device__ __forceinline__ SpecArgs spec_member(const SpecArgs &a, const SpecEns
     return m;
 }
 
+// Perturbed-parameter ensembles (qg_mi355_sweep.h) whose members differ in R_d: the Helmholtz
+// coefficient tables (coef, crr, ccs, cr: functions of alpha[1] = -1/R_d^2) and the input
+// projection pin_in (Derived::Pinv: R_d-free in exact arithmetic, but computed from S1, S2, so
+// its bits follow R_d) are the member's own too.  Everything else is SpecEns's.
+struct SpecSweep {
+    SpecEns ens;
+    int64_t tables;     // bytes between two members' coefficient tables (coef | crr | ccs | cr)
+    const double *pin;  // [members][4] pin_in
+};
+
+__device__ __forceinline__ SpecArgs spec_member(const SpecArgs &a, const SpecSweep &e, int b) {
+    SpecArgs m = spec_member(a, e.ens, b);
+    const int64_t to = e.tables * b;
+    m.coef = ens_off(a.coef, to);
+    m.crr = ens_off(a.crr, to);
+    m.ccs = ens_off(a.ccs, to);
+    m.cr = ens_off(a.cr, to);
+    const double *pin = e.pin + 4 * (size_t)b;
+    m.pin_in[0] = pin[0];
+    m.pin_in[1] = pin[1];
+    m.pin_in[2] = pin[2];
+    m.pin_in[3] = pin[3];
+    return m;
+}
+
 // ------------------------------------------------------------------------------------
 // pass A: project + row DFT + chunk-local backward filter (one workgroup per chunk)
 // ------------------------------------------------------------------------------------
@@ -2429,22 +2454,24 @@ static int launch_pass(bool passB, const SpecArgs &a, hipStream_t s) {
 }
 
 // the batched passes of an ensemble (F64, M = 2^k in 8..2048): grid (chunks, members)
-template <int N>
-static int launch_pass_ens(bool passB, const SpecArgs &a, const SpecEns &e, int nmembers, hipStream_t s) {
+// (E: SpecEns, or SpecSweep for members with their own coefficient tables)
+template <int N, class E>
+static int launch_pass_ens(bool passB, const SpecArgs &a, const E &e, int nmembers, hipStream_t s) {
     const size_t lds = sizeof(double2) * (size_t)FftPlan<N, Geo<N>::T>::LDS;
     const dim3 grid((unsigned)a.Nc, (unsigned)nmembers);
     if (passB) {
-        QG_HIP(hipFuncSetAttribute((const void *)spec_passB<N, double, SpecEns>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        QG_HIP(hipFuncSetAttribute((const void *)spec_passB<N, double, E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         spec_passB<N, double><<<grid, Geo<N>::T, lds, s>>>(a, e);
     } else {
-        QG_HIP(hipFuncSetAttribute((const void *)spec_passA<N, double, SpecEns>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        QG_HIP(hipFuncSetAttribute((const void *)spec_passA<N, double, E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         spec_passA<N, double><<<grid, Geo<N>::T, lds, s>>>(a, e);
     }
     QG_LAUNCH_CHECK();
     return QG_OK;
 }
 
-static int dispatch_pass_ens(bool passB, const SpecArgs &a, const SpecEns &e, int nmembers, hipStream_t s) {
+template <class E>
+static int dispatch_pass_ens(bool passB, const SpecArgs &a, const E &e, int nmembers, hipStream_t s) {
     switch (a.M) {
         case 8: return launch_pass_ens<8>(passB, a, e, nmembers, s);
         case 16: return launch_pass_ens<16>(passB, a, e, nmembers, s);
@@ -2741,6 +2768,55 @@ static int pick_chunk(int64_t M, int64_t P, int req) {
 
 static size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
+// The per-(system, k) coefficients [2][KS] of the solves with shifts alpha[2] on a's geometry
+// (M, P, P_total, L, KH, KS, dx, pinned0), in long double.  Once per solver; once per member for
+// an ensemble whose members have their own alpha (init_member_tables).
+static int build_coef(const SpecArgs &a, const double alpha[2], std::vector<Coef> &coef) {
+    const long double twopi = 6.283185307179586476925286766559L;
+    const int64_t M = a.M, P = a.P, P_total = a.P_total;
+    const int L = a.L, KS = a.KS;
+    const double dx = a.dx;
+    coef.assign(2 * (size_t)KS, Coef{});
+    std::memset(coef.data(), 0, sizeof(Coef) * coef.size());
+    for (int s = 0; s < 2; ++s)
+        for (int k = 0; k < a.KH; ++k) {
+            Coef &cf = coef[s * KS + k];
+            if (s == 0 && a.pinned0 && k == 0) continue;  // singular line, r = 0 marker
+            const long double th = twopi * (long double)k / (long double)M;
+            const long double sh = sinl(th / 2);
+            const long double d = 2 * sh * sh - (long double)alpha[s] * (long double)dx * (long double)dx / 2;
+            if (!(d > 0)) return QG_ERR_UNSUPPORTED;  // singular (alpha = 0 unpinned) or alpha > 0
+            // r = rho - sqrt(rho^2 - 1) with rho = 1 + d, in cancellation-free form
+            const long double sq = sqrtl(d * (d + 2));
+            const long double r = 1 / ((1 + d) + sq);
+            const long double lr = -log1pl(d + sq);
+            if (!(r > 1e-300L)) return QG_ERR_UNSUPPORTED;  // |alpha| dx^2 beyond double range
+            cf.r = (double)r;
+            cf.rinv = (double)(1 / r);
+            cf.lr = (double)lr;
+            cf.q = (double)expl(L * lr);
+            cf.qm1 = (double)expl((L - 1) * lr);
+            if (-(L - 1) * lr > 600) return QG_ERR_UNSUPPORTED;  // r^-(L-1) scaling would overflow
+            cf.gam = (double)(r * expm1l(2 * L * lr) / expm1l(2 * lr));
+            cf.rP = (double)expl((long double)P * lr);
+            cf.gamP = (double)(r * expm1l(2 * (long double)P * lr) / expm1l(2 * lr));
+            cf.cs = (double)(-r * (long double)dx * (long double)dx / (long double)M);
+            cf.inv1mrPt = (double)(-1 / expm1l((long double)P_total * lr));
+        }
+    return QG_OK;
+}
+
+// the k-order hot tables of coef: hot[0 .. 4 KS) = (r, 1/r) pairs (crr), [4 KS .. 6 KS) = cs
+// (ccs), [6 KS .. 8 KS) = r (cr)
+static void fill_hot(const std::vector<Coef> &coef, int KS, double *hot) {
+    for (size_t i = 0; i < 2 * (size_t)KS; ++i) {
+        hot[2 * i] = coef[i].r;
+        hot[2 * i + 1] = coef[i].rinv;
+        hot[4 * KS + i] = coef[i].cs;
+        hot[6 * KS + i] = coef[i].r;
+    }
+}
+
 int SpectralSolver::init(int64_t M, int64_t P, int64_t P_total, int rank, int nranks, double dx,
                          const double alpha[2], int pinned0, const double pin_in[4], const double pin_out[4],
                          int chunk_rows, int f32, int nmembers) {
@@ -2797,33 +2873,8 @@ int SpectralSolver::init(int64_t M, int64_t P, int64_t P_total, int rank, int nr
         const long double ang = twopi * (long double)m / (long double)M;
         tw[m] = make_double2((double)cosl(ang), (double)-sinl(ang));
     }
-    std::vector<Coef> coef(2 * (size_t)KS);
-    std::memset(coef.data(), 0, sizeof(Coef) * coef.size());
-    for (int s = 0; s < 2; ++s)
-        for (int k = 0; k < a.KH; ++k) {
-            Coef &cf = coef[s * KS + k];
-            if (s == 0 && pinned0 && k == 0) continue;  // singular line, r = 0 marker
-            const long double th = twopi * (long double)k / (long double)M;
-            const long double sh = sinl(th / 2);
-            const long double d = 2 * sh * sh - (long double)alpha[s] * (long double)dx * (long double)dx / 2;
-            if (!(d > 0)) return QG_ERR_UNSUPPORTED;  // singular (alpha = 0 unpinned) or alpha > 0
-            // r = rho - sqrt(rho^2 - 1) with rho = 1 + d, in cancellation-free form
-            const long double sq = sqrtl(d * (d + 2));
-            const long double r = 1 / ((1 + d) + sq);
-            const long double lr = -log1pl(d + sq);
-            if (!(r > 1e-300L)) return QG_ERR_UNSUPPORTED;  // |alpha| dx^2 beyond double range
-            cf.r = (double)r;
-            cf.rinv = (double)(1 / r);
-            cf.lr = (double)lr;
-            cf.q = (double)expl(L * lr);
-            cf.qm1 = (double)expl((L - 1) * lr);
-            if (-(L - 1) * lr > 600) return QG_ERR_UNSUPPORTED;  // r^-(L-1) scaling would overflow
-            cf.gam = (double)(r * expm1l(2 * L * lr) / expm1l(2 * lr));
-            cf.rP = (double)expl((long double)P * lr);
-            cf.gamP = (double)(r * expm1l(2 * (long double)P * lr) / expm1l(2 * lr));
-            cf.cs = (double)(-r * (long double)dx * (long double)dx / (long double)M);
-            cf.inv1mrPt = (double)(-1 / expm1l((long double)P_total * lr));
-        }
+    std::vector<Coef> coef;
+    QG_CHECK(build_coef(a, alpha, coef));
 
     // ---- device memory ---------------------------------------------------------------
     const size_t n_tw = align_up(sizeof(double2) * M);
@@ -2936,12 +2987,7 @@ int SpectralSolver::init(int64_t M, int64_t P, int64_t P_total, int rank, int nr
     {
         // [2][KS] (r, 1/r) pairs, [2][KS] cs, [2][KS] r; slot order: [2][KS] (r, 1/r), [2][KS] r
         std::vector<double> hot(14 * (size_t)KS);
-        for (size_t i = 0; i < 2 * (size_t)KS; ++i) {
-            hot[2 * i] = coef[i].r;
-            hot[2 * i + 1] = coef[i].rinv;
-            hot[4 * KS + i] = coef[i].cs;
-            hot[6 * KS + i] = coef[i].r;
-        }
+        fill_hot(coef, KS, hot.data());
         if (M == lx::N || M == 2 * lx::N) {
             const int lines = M == lx::N ? 4 : 8;  // per thread and system
             for (int s = 0; s < 2; ++s)
@@ -3027,6 +3073,39 @@ int SpectralSolver::init_twopoint(int64_t M, int64_t P, int nranks, double dx, c
 
 SpectralSolver::~SpectralSolver() {
     if (mem_) (void)hipFree(mem_);
+    if (sweep_mem_) (void)hipFree(sweep_mem_);
+}
+
+// An ensemble's solver with one Helmholtz shift and one input projection per member: member b's
+// tables are built exactly as init() builds a single solver's from alpha = {0, alpha1[b]} (the
+// same function on the same geometry), so its solve is that solver's.  Layout per member:
+// coef [2][KS] | crr | ccs | cr, `sweep_tables_` bytes apart; then pin_in [members][4].
+int SpectralSolver::init_member_tables(const double *alpha1, const double *pin_in) {
+    if (!mem_) return QG_ERR_NOT_BOUND;
+    if (!alpha1 || !pin_in || sweep_mem_) return QG_ERR_INVALID_ARG;
+    if (a_.two || !supports_members(a_.M, a_.P, a_.nranks, a_.f32)) return QG_ERR_UNSUPPORTED;
+    const int KS = a_.KS;
+    const size_t n_coef = align_up(sizeof(Coef) * 2 * (size_t)KS), n_hot = align_up(sizeof(double) * 8 * (size_t)KS);
+    const size_t n_tab = n_coef + n_hot, n_pin = align_up(sizeof(double) * 4 * (size_t)nmembers_);
+    std::vector<char> host(n_tab * (size_t)nmembers_ + n_pin, 0);
+    std::vector<Coef> coef;
+    for (int b = 0; b < nmembers_; ++b) {
+        const double alpha[2] = {0.0, alpha1[b]};
+        QG_CHECK(build_coef(a_, alpha, coef));
+        char *t = host.data() + n_tab * (size_t)b;
+        std::memcpy(t, coef.data(), sizeof(Coef) * coef.size());
+        fill_hot(coef, KS, reinterpret_cast<double *>(t + n_coef));
+    }
+    std::memcpy(host.data() + n_tab * (size_t)nmembers_, pin_in, sizeof(double) * 4 * (size_t)nmembers_);
+    if (hipMalloc(&sweep_mem_, host.size()) != hipSuccess) {
+        sweep_mem_ = nullptr;
+        return QG_ERR_ALLOC;
+    }
+    QG_HIP(hipMemcpy(sweep_mem_, host.data(), host.size(), hipMemcpyHostToDevice));
+    sweep_tables_ = n_tab;
+    sweep_hot_ = n_coef;
+    bytes_ += host.size();
+    return QG_OK;
 }
 
 // The carry launch: k-blocks plus the extra column, and the kernel variant (spec_carry<4>, two
@@ -3113,18 +3192,28 @@ int SpectralSolver::solve_members(const void *in1, const void *in2, void *out1, 
     a.fuse_pin = 1;
     a.npin = (a.KH + CARRY_KB - 1) / CARRY_KB;
     const SpecEns e{(int64_t)member_bytes_, field_stride_bytes};
-    QG_CHECK(dispatch_pass_ens(false, a, e, nmembers_, s));
-    {
+    auto run = [&](const auto &pack) -> int {
+        QG_CHECK(dispatch_pass_ens(false, a, pack, nmembers_, s));
         unsigned nkb = 0;
         bool two_per_cu = false;
         QG_CHECK(carry_geometry(a, &nkb, &two_per_cu));
         const dim3 grid(nkb, 2, (unsigned)nmembers_);
-        if (two_per_cu) spec_carry<4><<<grid, 64 * CARRY_WAVES, 0, s>>>(a, e);
-        else spec_carry<1><<<grid, 64 * CARRY_WAVES, 0, s>>>(a, e);
-    }
-    QG_LAUNCH_CHECK();
-    QG_CHECK(dispatch_pass_ens(true, a, e, nmembers_, s));
-    return QG_OK;
+        if (two_per_cu) spec_carry<4><<<grid, 64 * CARRY_WAVES, 0, s>>>(a, pack);
+        else spec_carry<1><<<grid, 64 * CARRY_WAVES, 0, s>>>(a, pack);
+        QG_LAUNCH_CHECK();
+        return dispatch_pass_ens(true, a, pack, nmembers_, s);
+    };
+    if (!sweep_mem_) return run(e);
+    // per-member tables (init_member_tables): member 0's, the others sweep_tables_ bytes apart
+    const char *t = static_cast<const char *>(sweep_mem_);
+    const double *hot = reinterpret_cast<const double *>(t + sweep_hot_);
+    a.coef = reinterpret_cast<const Coef *>(t);
+    a.crr = reinterpret_cast<const double2 *>(hot);
+    a.ccs = hot + 4 * a.KS;
+    a.cr = hot + 6 * a.KS;
+    const SpecSweep w{e, (int64_t)sweep_tables_,
+                      reinterpret_cast<const double *>(t + sweep_tables_ * (size_t)nmembers_)};
+    return run(w);
 }
 
 }  // namespace qg

@@ -129,6 +129,10 @@ public:
     static bool supports_members(int64_t M, int64_t P, int nranks, int f32);
     int solve_members(const void *in1, const void *in2, void *out1, void *out2, int64_t field_stride_bytes,
                       hipStream_t s);
+    // Members with their own Helmholtz shift (after init with nmembers): alpha1[b] replaces
+    // alpha[1] and pin_in[4 b .. 4 b + 4) the input projection for member b (host arrays);
+    // solve_members then runs every member on its own coefficient tables.
+    int init_member_tables(const double *alpha1, const double *pin_in);
     int members() const { return nmembers_; }
     // pass A can write the zcopy fields (power-of-two rows: the FFT and wide-row passes)
     bool fuses_input_copy() const { return !a_.two && a_.M >= 8 && a_.M <= 8192 && (a_.M & (a_.M - 1)) == 0; }
@@ -145,6 +149,9 @@ private:
     size_t bytes_ = 0;
     int nmembers_ = 1;         // scratch blocks (U .. pinpart) allocated
     size_t member_bytes_ = 0;  // bytes of one
+    void *sweep_mem_ = nullptr;  // per-member coefficient tables and pin_in (init_member_tables)
+    size_t sweep_tables_ = 0;    // bytes of one member's tables
+    size_t sweep_hot_ = 0;       // offset of crr | ccs | cr in them
 };
 
 }  // namespace qg

@@ -963,10 +963,12 @@ int launch_fill_ghost_cols(double *b, int64_t M, int64_t P, hipStream_t s) {
 // ------------------------------------------------------------------------------------
 // one point (i, j) of one layer: loads, tendency, AB3 update, stores; returns the centre
 // values the certification uses (zeta, lap(psi), psi).  off: elements added to every field
-// pointer of `a` (an ensemble member's block; 0 for a single context)
-template <class T>
+// pointer of `a` (an ensemble member's block; 0 for a single context).  MEMBER: the record *mr's
+// (visc, U, r, beta, wind) stand in for a's (a perturbed-parameter ensemble's member); a
+// compile-time switch, so the other instantiations are the code they were
+template <class T, bool MEMBER = false>
 __device__ __forceinline__ void direct_point(const TendArgsT<T> &a, int layer, int i, int j, T &zc_out, T &L0_out,
-                                             T &P0_out, const size_t off = 0) {
+                                             T &P0_out, const size_t off = 0, const TendMember *mr = nullptr) {
     const int M = (int)a.M, P = (int)a.P;
     const int64_t ld = a.ld;
     const T *psi = a.psi[layer] + off, *zeta = a.zeta[layer] + off;
@@ -975,7 +977,8 @@ __device__ __forceinline__ void direct_point(const TendArgsT<T> &a, int layer, i
     const T dx = (T)a.dx, idx = T(1) / dx, idx2 = idx * idx;
     const T cdc = T(0.5) * idx;
     const T den = T(12) * (dx * dx);
-    const T visc = (T)a.visc, dtT = (T)a.dt, Ut = (T)a.U, rt = (T)a.r;
+    const T visc = (T)(MEMBER ? mr->visc : a.visc), dtT = (T)a.dt, Ut = (T)(MEMBER ? mr->U : a.U),
+            rt = (T)(MEMBER ? mr->r : a.r);
     const bool small = M < 8;
     auto wx = [&](int x) -> int {
         if (small) return ((x % M) + M) % M;
@@ -1001,13 +1004,17 @@ __device__ __forceinline__ void direct_point(const TendArgsT<T> &a, int layer, i
     const T biharm = ((((lap(-1, 0) + lap(1, 0)) - T(4) * L0) + lap(0, -1)) + lap(0, 1)) * idx2;
     const T v_term = visc * biharm;
     const T J_term = arakawa_point<T>(Z, S, den);
-    const T bl = (T)a.beta[layer];
+    const T bl = (T)(MEMBER ? mr->beta[layer] : a.beta[layer]);
     const T beta_term = bl * (cdc * (S(1, 0) - S(-1, 0)));
     T last;
     if (layer == 0) last = Ut * (cdc * (Z(1, 0) - Z(-1, 0)));
     else last = rt * L0;
     T F = ((v_term - J_term) - beta_term) - last;
-    if (layer == 0 && a.wind) F = F + (T)a.wind[j];
+    if constexpr (MEMBER) {
+        if (layer == 0 && mr->wind) F = F + (T)mr->wind[j];
+    } else {
+        if (layer == 0 && a.wind) F = F + (T)a.wind[j];
+    }
     const T zcen = Z(0, 0);
     T zn, f1c = 0, f2c = 0;
     if (a.ab3) {
@@ -1066,6 +1073,31 @@ __global__ __launch_bounds__(256) void tendency_direct_ens_kernel(TendArgsT<doub
     if (i >= (int)a.M || j >= a.j1) return;  // no barriers below
     double zc, L0, P0;
     direct_point(a, layer, i, j, zc, L0, P0, off);
+}
+
+// Perturbed-parameter ensembles (qg_mi355_sweep.h): tendency_direct_ens_kernel with the five
+// model scalars and the wind table of the workgroup's member read from its 64-byte record
+// (workgroup-uniform: scalar loads) in place of the arguments'.  direct_point takes the record
+// beside the arguments: a patched copy of them would leave the kernel-argument segment for
+// scratch (472 bytes per lane on the compiler's resource report).  The point itself is
+// direct_point, so a member's arithmetic is a single context's with those parameters.
+// rec[m].wind is null for a member without wind: its F never sees the "+ w_j" (which would turn
+// a -0.0 into +0.0).
+__global__ __launch_bounds__(256) void tendency_direct_sweep_kernel(TendArgsT<double> a, int nx, int ny, int64_t mstride,
+                                                                    const TendMember *rec) {
+    const int b = xcd_logical_id();
+    const int x = b % nx;
+    int r = b / nx;
+    const int y = r % ny;
+    r /= ny;
+    const int layer = r & 1;
+    const int m = r >> 1;  // workgroup-uniform
+    const size_t off = (size_t)m * (size_t)mstride;
+    const int i = x * 64 + (int)(threadIdx.x & 63);
+    const int j = a.j0 + 4 * y + (int)(threadIdx.x >> 6);
+    if (i >= (int)a.M || j >= a.j1) return;  // no barriers below
+    double zc, L0, P0;
+    direct_point<double, true>(a, layer, i, j, zc, L0, P0, off, rec + m);
 }
 
 // The certifying form of the cache-resident kernel (PCG, one rank, small grids): each thread
@@ -1288,6 +1320,18 @@ int launch_tendency_members(const TendArgsT<double> &a, int nmembers, int64_t me
     const int64_t blocks = (int64_t)nx * ny * 2 * nmembers;
     if (blocks > 0x7fffffff) return QG_ERR_UNSUPPORTED;
     tendency_direct_ens_kernel<<<(unsigned)blocks, 256, 0, s>>>(a, nx, ny, member_stride);
+    QG_LAUNCH_CHECK();
+    return QG_OK;
+}
+
+// launch_tendency_members with per-member parameters: rec = device table of nmembers records
+int launch_tendency_sweep(const TendArgsT<double> &a, int nmembers, int64_t member_stride, const TendMember *rec,
+                          hipStream_t s) {
+    if (nmembers < 1 || !rec || a.j1 <= a.j0 || a.j3 > a.j2) return QG_ERR_INVALID_ARG;
+    const int nx = (int)((a.M + 63) / 64), ny = (a.j1 - a.j0 + 3) / 4;
+    const int64_t blocks = (int64_t)nx * ny * 2 * nmembers;
+    if (blocks > 0x7fffffff) return QG_ERR_UNSUPPORTED;
+    tendency_direct_sweep_kernel<<<(unsigned)blocks, 256, 0, s>>>(a, nx, ny, member_stride, rec);
     QG_LAUNCH_CHECK();
     return QG_OK;
 }

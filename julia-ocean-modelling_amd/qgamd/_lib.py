@@ -53,6 +53,14 @@ class QgDiag(C.Structure):
                 ("energy", C.c_double * 2), ("interface", C.c_double), ("reserved", C.c_double)]
 
 
+class QgMemberParams(C.Structure):
+    """Mirror of ``struct qg_member_params`` (include/qg_mi355_sweep.h): one member's own values."""
+
+    _fields_ = [("U", C.c_double), ("beta", C.c_double), ("r", C.c_double), ("visc", C.c_double),
+                ("R_d", C.c_double), ("initial_kick", C.c_double), ("wind_tau0", C.c_double),
+                ("reserved", C.c_double)]
+
+
 class QgStats(C.Structure):
     _fields_ = [("iters", C.c_int32 * 2), ("relres", C.c_double * 2), ("delta", C.c_double),
                 ("pin", C.c_double)]
@@ -124,6 +132,11 @@ SIGNATURES = [
     ("qg_ens_canonicalize", C.c_int, [_vp]),
     ("qg_ens_diagnostics", C.c_int, [_vp, C.POINTER(QgDiag)]),
     ("qg_ens_synchronize", C.c_int, [_vp]),
+    # include/qg_mi355_sweep.h
+    ("qg_member_params_default", C.c_int, [C.POINTER(QgParams), C.POINTER(QgMemberParams)]),
+    ("qg_ens_create_sweep", C.c_int, [C.POINTER(QgParams), C.POINTER(QgMemberParams), C.c_int, C.c_int, _vp,
+                                      C.POINTER(_vp)]),
+    ("qg_ens_member_params", C.c_int, [_vp, C.c_int, C.POINTER(QgMemberParams)]),
 ]
 
 _lib = None

@@ -22,6 +22,8 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import dataclasses
+import itertools
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -556,9 +558,27 @@ def ensemble_seeds(nmembers):
     return [(SEED_LAYER1 + 2 * b, SEED_LAYER2 + 2 * b) for b in range(int(nmembers))]
 
 
+MEMBER_KEYS = ("U", "beta", "r", "visc", "R_d", "initial_kick", "wind_tau0")
+
+
+def sweep_members(**axes):
+    """The Cartesian product of value lists as a ``members`` list for :class:`Ensemble`:
+    ``sweep_members(U=[a, b], r=[c, d, e])`` is the 6 mappings {U: a, r: c}, {U: a, r: d}, ...,
+    {U: b, r: e} -- row-major in the keyword order (the last keyword varies fastest)."""
+    for k in axes:
+        if k not in MEMBER_KEYS:
+            raise ValueError(f"unknown member parameter {k!r} (one of {', '.join(MEMBER_KEYS)})")
+    keys = list(axes)
+    return [dict(zip(keys, vals)) for vals in itertools.product(*[list(axes[k]) for k in keys])]
+
+
 class Ensemble:
     """B members of one model -- same parameters, different states -- advanced together: every
     step is the four kernel launches a :class:`State` needs for one member (qg_ens_*).
+
+    With ``members`` (include/qg_mi355_sweep.h) each member may carry its own U, beta, r, visc,
+    R_d, initial_kick and wind_tau0: member b is then bit for bit a State of
+    :meth:`member_model` (b) with wind :meth:`member_wind` (b).
 
     ``zeta``, ``psi``, ``f_store`` are (B, 3, 2, P+2, M+2) float64 tensors (the Julia
     (M+2, P+2, 2, 3, B) arrays); member b's block is a :class:`State`'s array, and after the same
@@ -566,15 +586,30 @@ class Ensemble:
     rotate with one set of heads for all members.  F64, spectral solver, one GPU, M a power of
     two in 8..2048, P >= 3 (QGError with QG_ERR_UNSUPPORTED otherwise)."""
 
-    def __init__(self, m, nmembers, seeds=None, chunk_rows=0, P_fwd=None, wind=None, device=None):
+    def __init__(self, m, nmembers, seeds=None, chunk_rows=0, P_fwd=None, wind=None, device=None, members=None):
         """seeds: a sequence of B (seed1, seed2) pairs to initialise with right away, or None
-        (call :meth:`initialise`, or fill the tensors, before stepping)."""
+        (call :meth:`initialise`, or fill the tensors, before stepping).  members: a sequence of
+        B mappings with keys from U, beta, r, visc, R_d, initial_kick, wind_tau0 (ValueError for
+        any other); a missing key takes the model's value, wind_tau0 overrides wind[0]."""
         _lib.lib()  # the HIP library first: no CPU fallback, fail before touching the device
         torch = _torch()
         self.model = m
         self.nmembers = int(nmembers)
         self.params = qg_params(m, _lib.QG_SOLVER_SPECTRAL, P_fwd, chunk_rows, wind=wind)
         self._ens = C.c_void_p()
+        mp = None
+        if members is not None:
+            members = list(members)
+            if len(members) != self.nmembers:
+                raise ValueError(f"{len(members)} member mappings for {self.nmembers} members")
+            mp = (_lib.QgMemberParams * self.nmembers)()
+            for b, kv in enumerate(members):
+                for k in kv:
+                    if k not in MEMBER_KEYS:
+                        raise ValueError(f"member {b}: unknown parameter {k!r} (one of {', '.join(MEMBER_KEYS)})")
+                call("qg_member_params_default", C.byref(self.params), C.byref(mp[b]))
+                for k, v in kv.items():
+                    setattr(mp[b], k, float(v))
         if device is None:
             self.device = torch.cuda.current_device()
         else:
@@ -584,8 +619,12 @@ class Ensemble:
             self.device = dev.index if dev.index is not None else torch.cuda.current_device()
         with torch.cuda.device(self.device):
             # created first: an unsupported configuration is refused before anything is allocated
-            call("qg_ens_create", C.byref(self.params), self.nmembers, int(self.device), _stream_ptr(),
-                 C.byref(self._ens))
+            if mp is None:
+                call("qg_ens_create", C.byref(self.params), self.nmembers, int(self.device), _stream_ptr(),
+                     C.byref(self._ens))
+            else:
+                call("qg_ens_create_sweep", C.byref(self.params), mp, self.nmembers, int(self.device),
+                     _stream_ptr(), C.byref(self._ens))
             shape = (self.nmembers, 3, 2, m.P + 2, m.M + 2)
             dev = torch.device("cuda", self.device)
             self.zeta = torch.zeros(shape, dtype=torch.float64, device=dev)
@@ -608,6 +647,23 @@ class Ensemble:
     def member(self, b):
         """The (zeta, psi, f_store) views of member b, each (3, 2, P+2, M+2)."""
         return self.zeta[b], self.psi[b], self.f_store[b]
+
+    def member_params(self, b):
+        """qg_ens_member_params: member b's seven values as a dict (the model's, without ``members``)."""
+        mp = _lib.QgMemberParams()
+        call("qg_ens_member_params", self._ens, int(b), C.byref(mp))
+        return {k: getattr(mp, k) for k in MEMBER_KEYS}
+
+    def member_model(self, b):
+        """The BaroclinicModel of member b: the ensemble's with b's values substituted."""
+        v = self.member_params(b)
+        v.pop("wind_tau0")
+        return dataclasses.replace(self.model, **v)
+
+    def member_wind(self, b):
+        """Member b's ``wind`` argument of a :class:`State`: (tau0, rho0), or None (no wind)."""
+        tau0 = self.member_params(b)["wind_tau0"]
+        return (tau0, self.params.wind_rho0) if tau0 != 0 else None
 
     def initialise(self, seeds=None):
         """qg_ens_initialise: initialise_model per member from B (seed1, seed2) pairs (default
@@ -657,7 +713,8 @@ class Ensemble:
 
 
 def run_ensemble_no_output(m, nmembers, nsteps=None, seeds=None, **kw):
-    """run_model_no_output for B members at once: init, floor(T/dt) steps; returns the Ensemble."""
+    """run_model_no_output for B members at once: init, floor(T/dt) steps; returns the Ensemble.
+    (``members=``: per-member parameters, see :class:`Ensemble`.)"""
     ens = Ensemble(m, nmembers, **kw).initialise(seeds)
     total = int(np.floor(m.T / m.dt)) if nsteps is None else int(nsteps)
     ens.run(1, total)

@@ -17,7 +17,8 @@ counts; exit status 1 if an old kernel differs or is gone.  Functions only the n
 counted, not judged.
 
 Record: the batched-ensemble change (qg_mi355_ensemble.h) left all 88 functions of
-qg_spectral.hip and all 20 of qg_stencil.hip identical and added 20 + 1.
+qg_spectral.hip and all 20 of qg_stencil.hip identical and added 20 + 1; the perturbed-parameter
+change (qg_mi355_sweep.h) left all 108 + 21 identical and added 20 + 1 (profiles/sweep/).
 """
 import re
 import sys
@@ -50,7 +51,8 @@ def unpack_name(name):
 
 
 def main(old_path, new_path):
-    old = functions(old_path)
+    # (both sides: the old file may already carry the packs)
+    old = {unpack_name(k): v for k, v in functions(old_path).items()}
     new = {unpack_name(k): v for k, v in functions(new_path).items()}
     same = bad = 0
     for k in sorted(old):
