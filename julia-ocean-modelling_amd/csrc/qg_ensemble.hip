@@ -16,6 +16,9 @@
 //   records differ, every R_d equal         launch_tendency_sweep + solve_members
 //   R_d differs                             launch_tendency_sweep + solve_members on per-member
 //                                           tables (SpectralSolver::init_member_tables)
+//
+// Statistics across the members (include/qg_mi355_stats.h): the three entry points are at the end
+// of this file, their kernels in qg_ens_stats.hip.
 #include <cmath>
 #include <cstring>
 #include <memory>
@@ -24,6 +27,7 @@
 
 #include "qg_common.hpp"
 #include "qg_mi355_ensemble.h"
+#include "qg_mi355_stats.h"
 #include "qg_mi355_sweep.h"
 #include "qg_spectral.hpp"
 
@@ -32,6 +36,13 @@ int diag_record_len();
 size_t diag_scratch_doubles();
 int launch_diagnostics(const void *z0, const void *z1, const void *p0, const void *p1, int esize, int64_t M,
                        int64_t P, double dx, double *scratch, double *rec, hipStream_t s);
+// qg_ens_stats.hip
+size_t ens_stats_scratch_doubles(int64_t M, int64_t P);
+size_t ens_stats_record_offset(int64_t M, int64_t P);
+int launch_ens_moments(const double *x, size_t n, size_t stride, int nmembers, double *mean, double *var,
+                       hipStream_t s);
+int launch_ens_spread(const double *z, const double *p, size_t F, int64_t M, int64_t P, size_t stride, int nmembers,
+                      double step, double *scratch, double *rec, hipStream_t s);
 }  // namespace qg
 
 using namespace qg;
@@ -50,6 +61,7 @@ struct qg_ens {
     std::vector<Derived> md;           // derive() of the base with member b's values substituted
     TendMember *rec = nullptr;         // device [nmembers] records: the sweep tendency (else null)
     double *diag = nullptr;    // diagnostics: partial records (reused member after member) | nmembers records
+    double *stats = nullptr;   // cross-member statistics: partial sums | one record (on first use)
     SpectralSolver spec;
     size_t F = 0;  // doubles per (M+2, P+2) field
 
@@ -213,6 +225,7 @@ int qg_ens_destroy(qg_ens *e) {
     if (e->wind) (void)hipFree(e->wind);
     if (e->rec) (void)hipFree(e->rec);
     if (e->diag) (void)hipFree(e->diag);
+    if (e->stats) (void)hipFree(e->stats);
     delete e;
     return QG_OK;
 }
@@ -364,6 +377,65 @@ int qg_ens_diagnostics(qg_ens *e, qg_diag *out) {
     QG_HIP(hipMemcpyAsync(out, recs, sizeof(qg_diag) * (size_t)e->nmembers, hipMemcpyDeviceToHost, e->stream));
     QG_HIP(hipStreamSynchronize(e->stream));
     for (int b = 0; b < e->nmembers; ++b) out[b].reserved = 0.0;
+    return QG_OK;
+}
+
+// ---- statistics across the members (include/qg_mi355_stats.h; kernels in qg_ens_stats.hip) ----
+static int ens_stats_scratch(qg_ens *e) {
+    if (e->stats) return QG_OK;
+    QG_HIP(hipSetDevice(e->device));
+    if (hipMalloc((void **)&e->stats, sizeof(double) * ens_stats_scratch_doubles(e->p.M, e->p.P)) != hipSuccess) {
+        e->stats = nullptr;
+        return QG_ERR_ALLOC;
+    }
+    return QG_OK;
+}
+
+// the spread record of the newest state -> rec (device)
+static int ens_spread_record(qg_ens *e, double step, double *rec) {
+    return launch_ens_spread(e->field(e->zeta, 0, e->heads[0]), e->field(e->psi, 0, e->heads[1]), e->F, e->p.M,
+                             e->p.P, e->member_stride(), e->nmembers, step, e->stats, rec, e->stream);
+}
+
+static bool aligned8(const void *p) { return reinterpret_cast<uintptr_t>(p) % sizeof(double) == 0; }
+
+int qg_ens_moments(qg_ens *e, int which, double *mean, double *var) {
+    if (!e || !mean || which < 0 || which > 1 || !aligned8(mean) || !aligned8(var)) return QG_ERR_INVALID_ARG;
+    if (!e->zeta) return QG_ERR_NOT_BOUND;
+    QG_HIP(hipSetDevice(e->device));
+    // one slot is both layers: 2 F points
+    return launch_ens_moments(e->field(which ? e->psi : e->zeta, 0, e->heads[which]), 2 * e->F, e->member_stride(),
+                              e->nmembers, mean, var, e->stream);
+}
+
+int qg_ens_spread(qg_ens *e, qg_spread *out) {
+    if (!e || !out) return QG_ERR_INVALID_ARG;
+    if (!e->zeta) return QG_ERR_NOT_BOUND;
+    static_assert(sizeof(qg_spread) == 16 * sizeof(double), "the record the kernels write");
+    QG_CHECK(ens_stats_scratch(e));
+    QG_HIP(hipSetDevice(e->device));
+    double *rec = e->stats + ens_stats_record_offset(e->p.M, e->p.P);
+    QG_CHECK(ens_spread_record(e, 0.0, rec));
+    QG_HIP(hipMemcpyAsync(out, rec, sizeof(qg_spread), hipMemcpyDeviceToHost, e->stream));
+    QG_HIP(hipStreamSynchronize(e->stream));
+    return QG_OK;
+}
+
+int qg_ens_run_recorded(qg_ens *e, int64_t first_step, int64_t nsteps, int64_t every, qg_spread *records,
+                        int64_t capacity, int64_t *nrecords) {
+    if (!e || first_step < 1 || nsteps < 0 || every < 1 || !records || !aligned8(records))
+        return QG_ERR_INVALID_ARG;
+    const int64_t n = nsteps / every;
+    if (capacity < n) return QG_ERR_INVALID_ARG;
+    if (!e->zeta) return QG_ERR_NOT_BOUND;
+    if (n > 0) QG_CHECK(ens_stats_scratch(e));
+    if (nrecords) *nrecords = n;
+    int64_t k = 0;
+    for (int64_t t = first_step; t < first_step + nsteps; ++t) {
+        QG_CHECK(qg_ens_step(e, t));
+        if ((t - first_step + 1) % every == 0)
+            QG_CHECK(ens_spread_record(e, (double)t, reinterpret_cast<double *>(records + k++)));
+    }
     return QG_OK;
 }
 

@@ -61,6 +61,15 @@ class QgMemberParams(C.Structure):
                 ("reserved", C.c_double)]
 
 
+class QgSpread(C.Structure):
+    """Mirror of ``struct qg_spread`` (include/qg_mi355_stats.h): 16 doubles, 128 bytes."""
+
+    _fields_ = [("zeta_var", C.c_double * 2), ("psi_var", C.c_double * 2), ("zeta_mean_sq", C.c_double * 2),
+                ("psi_mean_sq", C.c_double * 2), ("energy_spread", C.c_double * 2),
+                ("energy_mean", C.c_double * 2), ("step", C.c_double), ("nmembers", C.c_double),
+                ("reserved", C.c_double * 2)]
+
+
 class QgStats(C.Structure):
     _fields_ = [("iters", C.c_int32 * 2), ("relres", C.c_double * 2), ("delta", C.c_double),
                 ("pin", C.c_double)]
@@ -137,6 +146,10 @@ SIGNATURES = [
     ("qg_ens_create_sweep", C.c_int, [C.POINTER(QgParams), C.POINTER(QgMemberParams), C.c_int, C.c_int, _vp,
                                       C.POINTER(_vp)]),
     ("qg_ens_member_params", C.c_int, [_vp, C.c_int, C.POINTER(QgMemberParams)]),
+    # include/qg_mi355_stats.h (records of qg_ens_run_recorded: a device pointer)
+    ("qg_ens_moments", C.c_int, [_vp, C.c_int, _dp, _dp]),
+    ("qg_ens_spread", C.c_int, [_vp, C.POINTER(QgSpread)]),
+    ("qg_ens_run_recorded", C.c_int, [_vp, _i64, _i64, _i64, _dp, _i64, C.POINTER(_i64)]),
 ]
 
 _lib = None

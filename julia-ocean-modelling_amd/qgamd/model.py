@@ -711,12 +711,77 @@ class Ensemble:
         return [{f: (list(getattr(r, f)) if f != "interface" else r.interface)
                  for f, _ in _lib.QgDiag._fields_ if f != "reserved"} for r in d]
 
+    # ---- statistics across the members (include/qg_mi355_stats.h) ----
+    def moments(self, which, var=True):
+        """qg_ens_moments: (mean, var) over the members of the newest ``which`` ("zeta" or
+        "psi"), point by point, as (2, P+2, M+2) tensors (layer, row, column; ghost ring
+        included); var is the unbiased variance, or None with ``var=False``.  One launch on the
+        current stream, no synchronisation.  The arithmetic (Welford's recurrence in member
+        order) is fixed by the header: the fields are reproducible bit for bit."""
+        torch = _torch()
+        w = {"zeta": 0, "psi": 1}[which]
+        shape = (2, self.model.P + 2, self.model.M + 2)
+        dev = self.zeta.device
+        mean = torch.empty(shape, dtype=torch.float64, device=dev)
+        v = torch.empty(shape, dtype=torch.float64, device=dev) if var else None
+        with torch.cuda.device(self.device):
+            call("qg_ens_moments", self._ens, w, _ptr(mean), _ptr(v) if var else None)
+        return mean, v
 
-def run_ensemble_no_output(m, nmembers, nsteps=None, seeds=None, **kw):
+    def spread(self):
+        """qg_ens_spread: the domain-integrated spread record of the newest state as a dict
+        (per-layer lists; ``step`` is 0).  Synchronous."""
+        r = _lib.QgSpread()
+        with _torch().cuda.device(self.device):
+            call("qg_ens_spread", self._ens, C.byref(r))
+        return spread_dicts([(C.c_double * SPREAD_LEN).from_buffer(r)])[0]
+
+    def run_recorded(self, first_step, nsteps, every):
+        """qg_ens_run_recorded: :meth:`run` that records the spread record after every
+        ``every``-th step on the device, without a host round trip.  Returns the
+        (nsteps // every, 16) float64 device tensor of records (rows in the field order of
+        qg_spread; :func:`spread_dicts` turns rows into dicts).  Not synchronised."""
+        torch = _torch()
+        if int(every) < 1:
+            raise ValueError(f"every = {every}: must be at least 1")
+        n = max(int(nsteps), 0) // int(every)
+        # (at least one row: a null pointer is refused also when no record is due)
+        rec = torch.zeros((max(n, 1), SPREAD_LEN), dtype=torch.float64, device=self.zeta.device)
+        got = C.c_int64()
+        with torch.cuda.device(self.device):
+            call("qg_ens_run_recorded", self._ens, int(first_step), int(nsteps), int(every), _ptr(rec), n,
+                 C.byref(got))
+        return rec[:got.value]
+
+
+SPREAD_LEN = C.sizeof(_lib.QgSpread) // 8
+
+
+def spread_dicts(records):
+    """Rows of 16 doubles (a records tensor of :meth:`Ensemble.run_recorded`, or any sequence of
+    rows) as dicts keyed by qg_spread's fields: per-layer lists, ``step`` and ``nmembers``."""
+    rows = records.cpu().tolist() if hasattr(records, "cpu") else [list(r) for r in records]
+    out = []
+    for row in rows:
+        d, k = {}, 0
+        for f, t in _lib.QgSpread._fields_:
+            n = getattr(t, "_length_", 0)
+            if f != "reserved":
+                d[f] = list(row[k:k + n]) if n else row[k]
+            k += n or 1
+        out.append(d)
+    return out
+
+
+def run_ensemble_no_output(m, nmembers, nsteps=None, seeds=None, record_every=None, **kw):
     """run_model_no_output for B members at once: init, floor(T/dt) steps; returns the Ensemble.
-    (``members=``: per-member parameters, see :class:`Ensemble`.)"""
+    (``members=``: per-member parameters, see :class:`Ensemble`.)  With ``record_every=k`` the
+    spread record is taken on the device after every k-th step: returns (ens, records), see
+    :meth:`Ensemble.run_recorded`."""
     ens = Ensemble(m, nmembers, **kw).initialise(seeds)
     total = int(np.floor(m.T / m.dt)) if nsteps is None else int(nsteps)
+    if record_every is not None:
+        return ens, ens.run_recorded(1, total, record_every)
     ens.run(1, total)
     return ens
 
