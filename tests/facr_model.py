@@ -1,7 +1,7 @@
 """Numpy model of the device spectral (FACR) solver -- test infrastructure.
 
-Mirrors, step for step, what julia-ocean-modelling_amd/csrc/qg_spectral.hip computes for one
-rank: x-DFT of z = f1 + i f2 per row, chunk-local backward filter u_j = cs F_j + r u_{j+1}
+Mirrors, step for step, what the solver's kernels (julia-ocean-modelling_amd/csrc/qg_spec_*.hip,
+launched by qg_spectral.hip) compute for one rank: x-DFT of z = f1 + i f2 per row, chunk-local backward filter u_j = cs F_j + r u_{j+1}
 with the two chunk summaries, segment scans to chunk carries, the rank record that is
 all-gathered, the cross-rank / periodic closure, the Poisson compatibility shift delta, the
 singular k = 0 Poisson line and the pin.  The checker for it is the exact DFT solve of the C

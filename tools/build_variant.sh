@@ -1,14 +1,19 @@
 #!/bin/bash
 # build the library from another source directory into lib/exp/NAME.so (A/B experiments; run
 # on the CPU side, the .so travels with the snapshot).  usage: tools/build_variant.sh NAME SRC_DIR [FLAGS...]
+# Every SRC_DIR/*.hip with the Makefile's flags for that file, at most 16 compiles at once.
 set -e
 NAME=$1; SRC=$2; shift 2
-PKG=/root/repo/julia-ocean-modelling_amd
-OUT=/tmp/variant_$NAME; rm -rf $OUT; mkdir -p $OUT $PKG/lib/exp
-for f in qg_stencil qg_spectral qg_pcg qg_capi qg_comm qg_diag qg_mg; do
-  X=""; [ $f = qg_stencil ] && X="-ffp-contract=off"
-  /opt/rocm/bin/hipcc -O3 -fPIC -std=c++17 --offload-arch=gfx950 -I/root/repo/include -I$SRC -Wall -Wno-unused-function $X "$@" -c $SRC/$f.hip -o $OUT/$f.o &
-done
-wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o $PKG/lib/exp/$NAME.so $OUT/*.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
+PKG=$ROOT/julia-ocean-modelling_amd
+ROCM=${ROCM:-/opt/rocm}
+OUT=$(mktemp -d); trap 'rm -rf "$OUT"' EXIT
+mkdir -p $PKG/lib/exp
+export HIPCC=$ROCM/bin/hipcc OUT SRC
+export FLAGS="-O3 -fPIC -std=c++17 --offload-arch=gfx950 -I$ROOT/include -I$SRC -Wall -Wno-unused-function $*"
+ls $SRC/*.hip | xargs -P 16 -I{} bash -c '
+  f=$(basename {} .hip); X=""
+  case $f in qg_stencil|qg_ens_stats) X="-ffp-contract=off";; esac
+  $HIPCC $FLAGS $X -c {} -o $OUT/$f.o'
+$HIPCC --offload-arch=gfx950 -shared -o $PKG/lib/exp/$NAME.so $OUT/*.o -L$ROCM/lib -lrccl -Wl,-rpath,$ROCM/lib
 ls -la $PKG/lib/exp/$NAME.so

@@ -9,6 +9,17 @@ file before and after to gfx950 assembly and compare each function's instruction
     hipcc $F -Ijulia-ocean-modelling_amd/csrc julia-ocean-modelling_amd/csrc/qg_spectral.hip -o new.s
     python tools/kernel_isa_diff.py old.s new.s        # (qg_stencil.hip: add -ffp-contract=off)
 
+A file split into several (or several files against their parent's one): compile each to its
+own .s, concatenate them, and compare with the single old.s; the function labels summed over
+the new files must also equal the old file's count (a kernel instantiated in two files would
+show in neither list, only there).
+
+    for f in julia-ocean-modelling_amd/csrc/qg_spec*.hip; do
+        hipcc $F -Ijulia-ocean-modelling_amd/csrc $f -o new/$(basename $f .hip).s; done
+    cat new/*.s > new.s
+    python tools/kernel_isa_diff.py old.s new.s
+    grep -c '^_Z[A-Za-z0-9_]*:' old.s new/*.s
+
 Instructions are compared as text after dropping comments and directives and renumbering local
 labels (their numbers depend on a function's position in the file).  A kernel template that
 gained a trailing, empty parameter pack mangles differently (`...EJEEEv...DpT1_` for `...EEEv...`):
@@ -18,7 +29,13 @@ counted, not judged.
 
 Record: the batched-ensemble change (qg_mi355_ensemble.h) left all 88 functions of
 qg_spectral.hip and all 20 of qg_stencil.hip identical and added 20 + 1; the perturbed-parameter
-change (qg_mi355_sweep.h) left all 108 + 21 identical and added 20 + 1 (profiles/sweep/).
+change (qg_mi355_sweep.h) left all 108 + 21 identical and added 20 + 1 (profiles/sweep/).  The
+split of qg_spectral.hip into one file per kernel family (qg_spec_*.hip: bluestein 15, carry 7,
+gen 22, half 6, pow2 40, pow2_ens 36, twopoint 2, and qg_spectral.hip itself 0 functions) left
+all 128 identical, differing or missing 0, new only 0, the labels summing to the old 128;
+qg_stencil.hip (untouched) 22 identical.  With the generic and the split passes in files of
+their own, the four generic kernels differed in the order of two scalar adds in the direct
+DFT's loop (the families share dft_at); they share qg_spec_gen.hip for that reason.
 """
 import re
 import sys

@@ -1,20 +1,18 @@
 """Add wall_clock64 phase stamps to spec_passA_half (the wide-row pass A) in a COPY of csrc
 (experiment builds only): python tools/stamps/add_stamps_half.py DIR.  Read back with
-tools/stamps/stamps_passA_half.py.  Per workgroup 256 slots: 0 entry, 1 rows start, then five
+tools/stamps/stamps_phases.py.  Per workgroup 256 slots: 0 entry, 1 rows start, then five
 per row (row start, projection done = prefetched row arrived, hook = stage 1 + T1 writes done,
 transform done, split + recurrence + u stores issued), 255 exit after the stores drained."""
 import sys
 
-p = sys.argv[1] + '/qg_spectral.hip'
+p = sys.argv[1] + '/qg_spec_half.hip'
 s = open(p).read()
 rep = [
     ('''namespace qg {
-
-constexpr int CARRY_WAVES = 8;''', '''namespace qg {
+''', '''namespace qg {
 __device__ unsigned long long g_stamp[1024 * 256];
 #define STAMP(slot) do { if (threadIdx.x == 0 && blockIdx.x < 1024) { unsigned long long _t = wall_clock64(); __builtin_nontemporal_store(_t, &g_stamp[blockIdx.x * 256 + (slot)]); } } while (0)
-
-constexpr int CARRY_WAVES = 8;'''),
+'''),
 ]
 a0, b0 = rep[0]
 assert s.count(a0) == 1
