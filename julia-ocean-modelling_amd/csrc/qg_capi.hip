@@ -11,6 +11,7 @@
 #include <new>
 
 #include "qg_common.hpp"
+#include "qg_mi355_spectra.h"
 #include "qg_pcg.hpp"
 #include "qg_spectral.hpp"
 
@@ -35,6 +36,12 @@ int diag_record_len();
 size_t diag_scratch_doubles();
 int launch_diagnostics(const void *z0, const void *z1, const void *p0, const void *p1, int esize, int64_t M,
                        int64_t P, double dx, double *scratch, double *rec, hipStream_t s);
+// qg_spectra.hip
+bool spectra_supports(int64_t M, int64_t P);
+size_t spectra_scratch_doubles(int64_t M, int64_t P, int nmembers);
+int launch_spectra_twiddles(double *scratch, int64_t M, hipStream_t s);
+int launch_spectra(const void *z, const void *p, int esize, size_t F, int64_t M, int64_t P, double dx, size_t stride,
+                   int nmembers, double *scratch, double *out, hipStream_t s);
 }  // namespace qg
 
 using namespace qg;
@@ -112,6 +119,7 @@ struct qg_ctx {
     double *wind = nullptr;  // [P] wind forcing of the local rows (qg_params.wind_tau0 != 0)
     double *diag = nullptr;  // diagnostics scratch: partial records | record | gathered records
     size_t diag_cap = 0;
+    double *spectra = nullptr;  // qg_spectra's scratch: twiddles | partial records (on first use)
     std::unique_ptr<SpectralSolver> spec;
     std::unique_ptr<PcgSolver> pcg;
     int last_status = QG_OK;  // of the last solve (PCG: QG_ERR_NOT_CONVERGED is kept here)
@@ -290,6 +298,7 @@ int qg_destroy(qg_ctx *c) {
     if (c->ov_ready) (void)hipEventDestroy(c->ov_ready);
     if (c->ov_halo) (void)hipEventDestroy(c->ov_halo);
     if (c->diag) (void)hipFree(c->diag);
+    if (c->spectra) (void)hipFree(c->spectra);
     if (c->wind) (void)hipFree(c->wind);
     drop_graphs(c);
     if (c->gstream) (void)hipStreamDestroy(c->gstream);
@@ -1197,6 +1206,52 @@ int qg_arakawa_J(const double *zeta, const double *psi, double *out, int64_t M, 
 int qg_fill_ghosts(double *b, int64_t M, int64_t P, void *stream) {
     if (!b || M < 1 || P < 1) return QG_ERR_INVALID_ARG;
     return launch_fill_ghosts(b, M, P, static_cast<hipStream_t>(stream));
+}
+
+// ---- zonal wavenumber spectra (include/qg_mi355_spectra.h; kernels in qg_spectra.hip) ------
+// the refusals that need the handle, in the header's order; then the scratch (on first use)
+static int spectra_ready(qg_ctx *c) {
+    if (!c->initialised || !c->zeta) return QG_ERR_NOT_BOUND;
+    if (c->distributed || c->nranks != 1 || !spectra_supports(c->p.M, c->p.P)) return QG_ERR_UNSUPPORTED;
+    if (c->spectra) return QG_OK;
+    QG_HIP(hipSetDevice(c->device));
+    if (hipMalloc((void **)&c->spectra, sizeof(double) * spectra_scratch_doubles(c->p.M, c->p.P, 1)) != hipSuccess) {
+        c->spectra = nullptr;
+        (void)hipGetLastError();
+        return QG_ERR_ALLOC;
+    }
+    return launch_spectra_twiddles(c->spectra, c->p.M, c->stream);
+}
+
+// the record of the newest state -> out (device); interior points only: no ghost flush
+static int spectra_record(qg_ctx *c, double *out) {
+    return launch_spectra(c->fieldv(c->zeta, 0, c->heads[0]), c->fieldv(c->psi, 0, c->heads[1]), (int)c->esize, c->F,
+                          c->p.M, c->p.P, c->p.dx, 0, 1, c->spectra, out, c->stream);
+}
+
+static bool aligned8(const void *p) { return reinterpret_cast<uintptr_t>(p) % sizeof(double) == 0; }
+
+int qg_spectra(qg_ctx *c, double *out) {
+    if (!c || !out || !aligned8(out)) return QG_ERR_INVALID_ARG;
+    QG_CHECK(spectra_ready(c));
+    QG_HIP(hipSetDevice(c->device));
+    return spectra_record(c, out);
+}
+
+int qg_run_spectra(qg_ctx *c, int64_t first_step, int64_t nsteps, int64_t every, double *records, int64_t capacity,
+                   int64_t *nrecords) {
+    if (!c || first_step < 1 || nsteps < 0 || every < 1 || !records || !aligned8(records)) return QG_ERR_INVALID_ARG;
+    const int64_t n = nsteps / every;
+    if (capacity < n) return QG_ERR_INVALID_ARG;
+    QG_CHECK(spectra_ready(c));
+    if (nrecords) *nrecords = n;
+    const size_t len = (size_t)QG_SPEC_LINES * (size_t)(c->p.M / 2 + 1);
+    int64_t k = 0;
+    for (int64_t t = first_step; t < first_step + nsteps; ++t) {
+        QG_CHECK(qg_step(c, t));
+        if ((t - first_step + 1) % every == 0) QG_CHECK(spectra_record(c, records + len * (size_t)k++));
+    }
+    return poll_pcg(c, true);  // as qg_run: a failed deferred certificate is reported by the run
 }
 
 }  // extern "C"

@@ -27,6 +27,7 @@
 
 #include "qg_common.hpp"
 #include "qg_mi355_ensemble.h"
+#include "qg_mi355_spectra.h"
 #include "qg_mi355_stats.h"
 #include "qg_mi355_sweep.h"
 #include "qg_spectral.hpp"
@@ -43,6 +44,12 @@ int launch_ens_moments(const double *x, size_t n, size_t stride, int nmembers, d
                        hipStream_t s);
 int launch_ens_spread(const double *z, const double *p, size_t F, int64_t M, int64_t P, size_t stride, int nmembers,
                       double step, double *scratch, double *rec, hipStream_t s);
+// qg_spectra.hip
+bool spectra_supports(int64_t M, int64_t P);
+size_t spectra_scratch_doubles(int64_t M, int64_t P, int nmembers);
+int launch_spectra_twiddles(double *scratch, int64_t M, hipStream_t s);
+int launch_spectra(const void *z, const void *p, int esize, size_t F, int64_t M, int64_t P, double dx, size_t stride,
+                   int nmembers, double *scratch, double *out, hipStream_t s);
 }  // namespace qg
 
 using namespace qg;
@@ -62,6 +69,7 @@ struct qg_ens {
     TendMember *rec = nullptr;         // device [nmembers] records: the sweep tendency (else null)
     double *diag = nullptr;    // diagnostics: partial records (reused member after member) | nmembers records
     double *stats = nullptr;   // cross-member statistics: partial sums | one record (on first use)
+    double *spectra = nullptr; // zonal spectra: twiddles | every member's partial records (on first use)
     SpectralSolver spec;
     size_t F = 0;  // doubles per (M+2, P+2) field
 
@@ -226,6 +234,7 @@ int qg_ens_destroy(qg_ens *e) {
     if (e->rec) (void)hipFree(e->rec);
     if (e->diag) (void)hipFree(e->diag);
     if (e->stats) (void)hipFree(e->stats);
+    if (e->spectra) (void)hipFree(e->spectra);
     delete e;
     return QG_OK;
 }
@@ -435,6 +444,52 @@ int qg_ens_run_recorded(qg_ens *e, int64_t first_step, int64_t nsteps, int64_t e
         QG_CHECK(qg_ens_step(e, t));
         if ((t - first_step + 1) % every == 0)
             QG_CHECK(ens_spread_record(e, (double)t, reinterpret_cast<double *>(records + k++)));
+    }
+    return QG_OK;
+}
+
+// ---- zonal wavenumber spectra (include/qg_mi355_spectra.h; kernels in qg_spectra.hip) ----
+// the refusals that need the handle, in the header's order; then the scratch (on first use)
+static int ens_spectra_ready(qg_ens *e) {
+    if (!e->zeta) return QG_ERR_NOT_BOUND;
+    if (!spectra_supports(e->p.M, e->p.P)) return QG_ERR_UNSUPPORTED;
+    if (e->spectra) return QG_OK;
+    QG_HIP(hipSetDevice(e->device));
+    if (hipMalloc((void **)&e->spectra, sizeof(double) * spectra_scratch_doubles(e->p.M, e->p.P, e->nmembers)) !=
+        hipSuccess) {
+        e->spectra = nullptr;
+        (void)hipGetLastError();
+        return QG_ERR_ALLOC;
+    }
+    return launch_spectra_twiddles(e->spectra, e->p.M, e->stream);
+}
+
+// every member's record of the newest state -> out (device): a single context's launches with
+// the member as the grid's second dimension
+static int ens_spectra_record(qg_ens *e, double *out) {
+    return launch_spectra(e->field(e->zeta, 0, e->heads[0]), e->field(e->psi, 0, e->heads[1]), (int)sizeof(double),
+                          e->F, e->p.M, e->p.P, e->p.dx, e->member_stride(), e->nmembers, e->spectra, out, e->stream);
+}
+
+int qg_ens_spectra(qg_ens *e, double *out) {
+    if (!e || !out || !aligned8(out)) return QG_ERR_INVALID_ARG;
+    QG_CHECK(ens_spectra_ready(e));
+    QG_HIP(hipSetDevice(e->device));
+    return ens_spectra_record(e, out);
+}
+
+int qg_ens_run_spectra(qg_ens *e, int64_t first_step, int64_t nsteps, int64_t every, double *records,
+                       int64_t capacity, int64_t *nrecords) {
+    if (!e || first_step < 1 || nsteps < 0 || every < 1 || !records || !aligned8(records)) return QG_ERR_INVALID_ARG;
+    const int64_t n = nsteps / every;
+    if (capacity < n) return QG_ERR_INVALID_ARG;
+    QG_CHECK(ens_spectra_ready(e));
+    if (nrecords) *nrecords = n;
+    const size_t len = (size_t)e->nmembers * QG_SPEC_LINES * (size_t)(e->p.M / 2 + 1);
+    int64_t k = 0;
+    for (int64_t t = first_step; t < first_step + nsteps; ++t) {
+        QG_CHECK(qg_ens_step(e, t));
+        if ((t - first_step + 1) % every == 0) QG_CHECK(ens_spectra_record(e, records + len * (size_t)k++));
     }
     return QG_OK;
 }

@@ -364,6 +364,27 @@ class State:
         return {f: (list(getattr(d, f)) if f != "interface" else d.interface)
                 for f, _ in _lib.QgDiag._fields_ if f != "reserved"}
 
+    # -- zonal wavenumber spectra (include/qg_mi355_spectra.h) ---------------------------
+    def spectra(self):
+        """qg_spectra: the zonal wavenumber spectra of the newest state as a (5, M/2+1) float64
+        device tensor -- rows in the order of :data:`SPECTRA_LINES`, column k the zonal
+        wavenumber :func:`spectra_wavenumbers` (M, dx)[k]; each row sums over k to the field of
+        the same name of :meth:`diagnostics`.  Enqueued on the current stream, not synchronised.
+        One rank, M a power of two in 8..2048."""
+        torch = _torch()
+        out = torch.empty((_lib.QG_SPEC_LINES, self.model.M // 2 + 1), dtype=torch.float64, device=self.zeta.device)
+        with torch.cuda.device(self.device):
+            call("qg_spectra", self._ctx, _ptr(out))
+        return out
+
+    def run_spectra(self, first_step, nsteps, every):
+        """qg_run_spectra: :meth:`run` (stepped on the stream) that records :meth:`spectra` after
+        every ``every``-th step on the device, without a host round trip.  Returns the
+        (nsteps // every, 5, M/2+1) float64 device tensor of records.  Not synchronised."""
+        self._need_transport()
+        return _run_spectra("qg_run_spectra", self._ctx, self.device, self.zeta.device,
+                            (_lib.QG_SPEC_LINES, self.model.M // 2 + 1), first_step, nsteps, every)
+
     # -- slot rotation -----------------------------------------------------------------
     def slot(self, which, logical):
         w = {"zeta": 0, "psi": 1, "f_store": 2}[which]
@@ -752,6 +773,51 @@ class Ensemble:
             call("qg_ens_run_recorded", self._ens, int(first_step), int(nsteps), int(every), _ptr(rec), n,
                  C.byref(got))
         return rec[:got.value]
+
+    # ---- zonal wavenumber spectra (include/qg_mi355_spectra.h) ----
+    def spectra(self):
+        """qg_ens_spectra: every member's zonal wavenumber spectra of the newest state as a
+        (B, 5, M/2+1) float64 device tensor; member b's block is bit for bit
+        :meth:`State.spectra` of a State holding member b's arrays.  One pair of launches for
+        all members on the current stream, not synchronised."""
+        torch = _torch()
+        out = torch.empty((self.nmembers, _lib.QG_SPEC_LINES, self.model.M // 2 + 1), dtype=torch.float64,
+                          device=self.zeta.device)
+        with torch.cuda.device(self.device):
+            call("qg_ens_spectra", self._ens, _ptr(out))
+        return out
+
+    def run_spectra(self, first_step, nsteps, every):
+        """qg_ens_run_spectra: :meth:`run` that records :meth:`spectra` after every ``every``-th
+        step on the device, without a host round trip.  Returns the (nsteps // every, B, 5, M/2+1)
+        float64 device tensor of records.  Not synchronised."""
+        return _run_spectra("qg_ens_run_spectra", self._ens, self.device, self.zeta.device,
+                            (self.nmembers, _lib.QG_SPEC_LINES, self.model.M // 2 + 1), first_step, nsteps, every)
+
+
+SPECTRA_LINES = ("energy_1", "energy_2", "enstrophy_1", "enstrophy_2", "interface")
+"""The rows of a spectra record (layers 1-based, as the reference counts them): rows 0-1 sum over
+k to ``diagnostics()["energy"]``, rows 2-3 to ``["enstrophy"]``, row 4 to ``["interface"]``."""
+SPECTRA_STRIP_CAP = _lib.QG_SPEC_MAX_STRIPS
+"""Row strips of the spectra kernel: min(P, this), a function of P only (qg_mi355_spectra.h)."""
+
+
+def spectra_wavenumbers(M, dx):
+    """The zonal wavenumbers 2 pi k / (M dx), k = 0 .. M/2, of the columns of a spectra record."""
+    return 2.0 * np.pi * np.arange(int(M) // 2 + 1) / (int(M) * float(dx))
+
+
+def _run_spectra(name, handle, device, tdev, shape, first_step, nsteps, every):
+    torch = _torch()
+    if int(every) < 1:
+        raise ValueError(f"every = {every}: must be at least 1")
+    n = max(int(nsteps), 0) // int(every)
+    # (at least one record: a null pointer is refused also when no record is due)
+    rec = torch.zeros((max(n, 1),) + tuple(shape), dtype=torch.float64, device=tdev)
+    got = C.c_int64()
+    with torch.cuda.device(device):
+        call(name, handle, int(first_step), int(nsteps), int(every), _ptr(rec), n, C.byref(got))
+    return rec[:got.value]
 
 
 SPREAD_LEN = C.sizeof(_lib.QgSpread) // 8

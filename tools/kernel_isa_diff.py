@@ -35,7 +35,9 @@ gen 22, half 6, pow2 40, pow2_ens 36, twopoint 2, and qg_spectral.hip itself 0 f
 all 128 identical, differing or missing 0, new only 0, the labels summing to the old 128;
 qg_stencil.hip (untouched) 22 identical.  With the generic and the split passes in files of
 their own, the four generic kernels differed in the order of two scalar adds in the direct
-DFT's loop (the families share dft_at); they share qg_spec_gen.hip for that reason.
+DFT's loop (the families share dft_at); they share qg_spec_gen.hip for that reason.  The zonal
+spectra (qg_mi355_spectra.h) left all 190 functions of the sixteen earlier files identical and
+added the 20 of qg_spectra.hip (profiles/spectra/).
 """
 import re
 import sys
