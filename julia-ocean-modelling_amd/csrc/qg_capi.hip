@@ -11,6 +11,7 @@
 #include <new>
 
 #include "qg_common.hpp"
+#include "qg_mi355_profiles.h"
 #include "qg_mi355_spectra.h"
 #include "qg_pcg.hpp"
 #include "qg_spectral.hpp"
@@ -42,6 +43,10 @@ size_t spectra_scratch_doubles(int64_t M, int64_t P, int nmembers);
 int launch_spectra_twiddles(double *scratch, int64_t M, hipStream_t s);
 int launch_spectra(const void *z, const void *p, int esize, size_t F, int64_t M, int64_t P, double dx, size_t stride,
                    int nmembers, double *scratch, double *out, hipStream_t s);
+// qg_profiles.hip
+bool profiles_supports(int64_t M, int64_t P);
+int launch_profiles(const void *z, const void *p, int esize, size_t F, int64_t M, int64_t P, double dx, size_t stride,
+                    int nmembers, double *out, hipStream_t s);
 }  // namespace qg
 
 using namespace qg;
@@ -1250,6 +1255,44 @@ int qg_run_spectra(qg_ctx *c, int64_t first_step, int64_t nsteps, int64_t every,
     for (int64_t t = first_step; t < first_step + nsteps; ++t) {
         QG_CHECK(qg_step(c, t));
         if ((t - first_step + 1) % every == 0) QG_CHECK(spectra_record(c, records + len * (size_t)k++));
+    }
+    return poll_pcg(c, true);  // as qg_run: a failed deferred certificate is reported by the run
+}
+
+// ---- zonal-mean profiles per latitude (include/qg_mi355_profiles.h; kernel in qg_profiles.hip) ----
+// the refusals that need the handle, in the header's order (no scratch: a row is complete in its
+// workgroup)
+static int profiles_ready(qg_ctx *c) {
+    if (!c->initialised || !c->zeta) return QG_ERR_NOT_BOUND;
+    if (c->distributed || c->nranks != 1 || !profiles_supports(c->p.M, c->p.P)) return QG_ERR_UNSUPPORTED;
+    return QG_OK;
+}
+
+// the record of the newest state -> out (device); interior points only: no ghost flush
+static int profiles_record(qg_ctx *c, double *out) {
+    return launch_profiles(c->fieldv(c->zeta, 0, c->heads[0]), c->fieldv(c->psi, 0, c->heads[1]), (int)c->esize, c->F,
+                           c->p.M, c->p.P, c->p.dx, 0, 1, out, c->stream);
+}
+
+int qg_profiles(qg_ctx *c, double *out) {
+    if (!c || !out || !aligned8(out)) return QG_ERR_INVALID_ARG;
+    QG_CHECK(profiles_ready(c));
+    QG_HIP(hipSetDevice(c->device));
+    return profiles_record(c, out);
+}
+
+int qg_run_profiles(qg_ctx *c, int64_t first_step, int64_t nsteps, int64_t every, double *records, int64_t capacity,
+                    int64_t *nrecords) {
+    if (!c || first_step < 1 || nsteps < 0 || every < 1 || !records || !aligned8(records)) return QG_ERR_INVALID_ARG;
+    const int64_t n = nsteps / every;
+    if (capacity < n) return QG_ERR_INVALID_ARG;
+    QG_CHECK(profiles_ready(c));
+    if (nrecords) *nrecords = n;
+    const size_t len = (size_t)QG_PROF_LINES * (size_t)c->p.P;
+    int64_t k = 0;
+    for (int64_t t = first_step; t < first_step + nsteps; ++t) {
+        QG_CHECK(qg_step(c, t));
+        if ((t - first_step + 1) % every == 0) QG_CHECK(profiles_record(c, records + len * (size_t)k++));
     }
     return poll_pcg(c, true);  // as qg_run: a failed deferred certificate is reported by the run
 }

@@ -27,6 +27,7 @@
 
 #include "qg_common.hpp"
 #include "qg_mi355_ensemble.h"
+#include "qg_mi355_profiles.h"
 #include "qg_mi355_spectra.h"
 #include "qg_mi355_stats.h"
 #include "qg_mi355_sweep.h"
@@ -50,6 +51,10 @@ size_t spectra_scratch_doubles(int64_t M, int64_t P, int nmembers);
 int launch_spectra_twiddles(double *scratch, int64_t M, hipStream_t s);
 int launch_spectra(const void *z, const void *p, int esize, size_t F, int64_t M, int64_t P, double dx, size_t stride,
                    int nmembers, double *scratch, double *out, hipStream_t s);
+// qg_profiles.hip
+bool profiles_supports(int64_t M, int64_t P);
+int launch_profiles(const void *z, const void *p, int esize, size_t F, int64_t M, int64_t P, double dx, size_t stride,
+                    int nmembers, double *out, hipStream_t s);
 }  // namespace qg
 
 using namespace qg;
@@ -490,6 +495,43 @@ int qg_ens_run_spectra(qg_ens *e, int64_t first_step, int64_t nsteps, int64_t ev
     for (int64_t t = first_step; t < first_step + nsteps; ++t) {
         QG_CHECK(qg_ens_step(e, t));
         if ((t - first_step + 1) % every == 0) QG_CHECK(ens_spectra_record(e, records + len * (size_t)k++));
+    }
+    return QG_OK;
+}
+
+// ---- zonal-mean profiles per latitude (include/qg_mi355_profiles.h; kernel in qg_profiles.hip) ----
+static int ens_profiles_ready(qg_ens *e) {
+    if (!e->zeta) return QG_ERR_NOT_BOUND;
+    if (!profiles_supports(e->p.M, e->p.P)) return QG_ERR_UNSUPPORTED;
+    return QG_OK;
+}
+
+// every member's record of the newest state -> out (device): a single context's launch with the
+// member as the grid's second dimension
+static int ens_profiles_record(qg_ens *e, double *out) {
+    return launch_profiles(e->field(e->zeta, 0, e->heads[0]), e->field(e->psi, 0, e->heads[1]), (int)sizeof(double),
+                           e->F, e->p.M, e->p.P, e->p.dx, e->member_stride(), e->nmembers, out, e->stream);
+}
+
+int qg_ens_profiles(qg_ens *e, double *out) {
+    if (!e || !out || !aligned8(out)) return QG_ERR_INVALID_ARG;
+    QG_CHECK(ens_profiles_ready(e));
+    QG_HIP(hipSetDevice(e->device));
+    return ens_profiles_record(e, out);
+}
+
+int qg_ens_run_profiles(qg_ens *e, int64_t first_step, int64_t nsteps, int64_t every, double *records,
+                        int64_t capacity, int64_t *nrecords) {
+    if (!e || first_step < 1 || nsteps < 0 || every < 1 || !records || !aligned8(records)) return QG_ERR_INVALID_ARG;
+    const int64_t n = nsteps / every;
+    if (capacity < n) return QG_ERR_INVALID_ARG;
+    QG_CHECK(ens_profiles_ready(e));
+    if (nrecords) *nrecords = n;
+    const size_t len = (size_t)e->nmembers * QG_PROF_LINES * (size_t)e->p.P;
+    int64_t k = 0;
+    for (int64_t t = first_step; t < first_step + nsteps; ++t) {
+        QG_CHECK(qg_ens_step(e, t));
+        if ((t - first_step + 1) % every == 0) QG_CHECK(ens_profiles_record(e, records + len * (size_t)k++));
     }
     return QG_OK;
 }

@@ -17,6 +17,7 @@ QG_ERR_INVALID_ARG, QG_ERR_UNSUPPORTED, QG_ERR_HIP, QG_ERR_NOT_BOUND = -1, -2, -
 QG_ERR_ALLOC, QG_ERR_RCCL, QG_ERR_NOT_CONVERGED = -5, -6, -7
 QG_ENS_MAX_MEMBERS = 65535
 QG_SPEC_LINES, QG_SPEC_MAX_STRIPS = 5, 64
+QG_PROF_LINES = 12
 QG_XBUF_TO_NEXT, QG_XBUF_TO_PREV, QG_XBUF_FROM_PREV, QG_XBUF_FROM_NEXT = 0, 1, 2, 3
 QG_SOLVER_SPECTRAL = 0
 QG_F64, QG_F32 = 0, 1
@@ -156,6 +157,11 @@ SIGNATURES = [
     ("qg_run_spectra", C.c_int, [_vp, _i64, _i64, _i64, _dp, _i64, C.POINTER(_i64)]),
     ("qg_ens_spectra", C.c_int, [_vp, _dp]),
     ("qg_ens_run_spectra", C.c_int, [_vp, _i64, _i64, _i64, _dp, _i64, C.POINTER(_i64)]),
+    # include/qg_mi355_profiles.h (outputs and records: device pointers)
+    ("qg_profiles", C.c_int, [_vp, _dp]),
+    ("qg_run_profiles", C.c_int, [_vp, _i64, _i64, _i64, _dp, _i64, C.POINTER(_i64)]),
+    ("qg_ens_profiles", C.c_int, [_vp, _dp]),
+    ("qg_ens_run_profiles", C.c_int, [_vp, _i64, _i64, _i64, _dp, _i64, C.POINTER(_i64)]),
 ]
 
 _lib = None

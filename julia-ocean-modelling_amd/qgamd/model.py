@@ -385,6 +385,28 @@ class State:
         return _run_spectra("qg_run_spectra", self._ctx, self.device, self.zeta.device,
                             (_lib.QG_SPEC_LINES, self.model.M // 2 + 1), first_step, nsteps, every)
 
+    # -- zonal-mean profiles per latitude (include/qg_mi355_profiles.h) -----------------
+    def profiles(self):
+        """qg_profiles: the per-latitude lines of the newest state as a (12, P) float64 device
+        tensor -- rows in the order of :data:`PROFILE_LINES` (see there for the table), column j
+        the interior row; rows 0-4 sum over j to the fields of the same name of
+        :meth:`diagnostics`.  Enqueued on the current stream, not synchronised.  One rank, any
+        M, P >= 3."""
+        torch = _torch()
+        out = torch.empty((_lib.QG_PROF_LINES, self.model.P), dtype=torch.float64, device=self.zeta.device)
+        with torch.cuda.device(self.device):
+            call("qg_profiles", self._ctx, _ptr(out))
+        return out
+
+    def run_profiles(self, first_step, nsteps, every):
+        """qg_run_profiles: :meth:`run` (stepped on the stream) that records :meth:`profiles`
+        after every ``every``-th step on the device, without a host round trip: the time-latitude
+        (Hovmoeller) array.  Returns the (nsteps // every, 12, P) float64 device tensor of
+        records.  Not synchronised."""
+        self._need_transport()
+        return _run_spectra("qg_run_profiles", self._ctx, self.device, self.zeta.device,
+                            (_lib.QG_PROF_LINES, self.model.P), first_step, nsteps, every)
+
     # -- slot rotation -----------------------------------------------------------------
     def slot(self, which, logical):
         w = {"zeta": 0, "psi": 1, "f_store": 2}[which]
@@ -793,6 +815,63 @@ class Ensemble:
         float64 device tensor of records.  Not synchronised."""
         return _run_spectra("qg_ens_run_spectra", self._ens, self.device, self.zeta.device,
                             (self.nmembers, _lib.QG_SPEC_LINES, self.model.M // 2 + 1), first_step, nsteps, every)
+
+
+    # ---- zonal-mean profiles per latitude (include/qg_mi355_profiles.h) ----
+    def profiles(self):
+        """qg_ens_profiles: every member's per-latitude lines of the newest state as a
+        (B, 12, P) float64 device tensor; member b's block is bit for bit :meth:`State.profiles`
+        of a State holding member b's arrays.  One launch for all members on the current stream,
+        not synchronised."""
+        torch = _torch()
+        out = torch.empty((self.nmembers, _lib.QG_PROF_LINES, self.model.P), dtype=torch.float64,
+                          device=self.zeta.device)
+        with torch.cuda.device(self.device):
+            call("qg_ens_profiles", self._ens, _ptr(out))
+        return out
+
+    def run_profiles(self, first_step, nsteps, every):
+        """qg_ens_run_profiles: :meth:`run` that records :meth:`profiles` after every
+        ``every``-th step on the device, without a host round trip.  Returns the
+        (nsteps // every, B, 12, P) float64 device tensor of records.  Not synchronised."""
+        return _run_spectra("qg_ens_run_profiles", self._ens, self.device, self.zeta.device,
+                            (self.nmembers, _lib.QG_PROF_LINES, self.model.P), first_step, nsteps, every)
+
+
+PROFILE_LINES = ("energy_1", "energy_2", "enstrophy_1", "enstrophy_2", "interface", "psi_mean_1", "psi_mean_2",
+                 "zeta_mean_1", "zeta_mean_2", "vort_flux_1", "vort_flux_2", "heat_flux")
+"""The rows of a profiles record (layers 1-based, as the reference counts them), each a function
+of the interior row j.  Interior i = 0..M-1, i -+ 1 and j + 1 wrap; px = psi_l(i+1,j) - psi_l(i,j),
+py = psi_l(i,j+1) - psi_l(i,j), v_l = (psi_l(i+1,j) - psi_l(i-1,j)) * 0.5/dx (the reference's cd):
+
+  rows 0, 1   energy[l]     1/2 sum_i (px^2 + py^2)
+  rows 2, 3   enstrophy[l]  1/2 dx^2 sum_i zeta_l^2
+  row  4      interface     1/2 dx^2 sum_i (psi_1 - psi_2)^2
+  rows 5, 6   psi_mean[l]   (1/M) sum_i psi_l
+  rows 7, 8   zeta_mean[l]  (1/M) sum_i zeta_l
+  rows 9, 10  vort_flux[l]  (1/M) sum_i v_l zeta_l
+  row  11     heat_flux     (1/M) sum_i 1/2 (v_1 + v_2) (psi_1 - psi_2)
+
+Rows 0-4 sum over j to ``diagnostics()["energy"]``, ``["enstrophy"]`` and ``["interface"]``;
+M dx^2 sum_j zeta_mean[l] is ``["zeta_sum"][l]``."""
+
+
+def zonal_wind(records, dx):
+    """The zonal-mean zonal wind of both layers from the ``psi_mean`` rows of profiles records:
+    u_l(j) = -(psi_mean_l(j+1) - psi_mean_l(j-1)) * 0.5/dx, rows wrapping.  ``records``: a
+    (..., 12, P) tensor or array with any leading dimensions; returns (..., 2, P) of its kind."""
+    pm = records[..., 5:7, :]
+    if isinstance(pm, np.ndarray):
+        return -(np.roll(pm, -1, axis=-1) - np.roll(pm, 1, axis=-1)) * (0.5 / float(dx))
+    return -(pm.roll(-1, -1) - pm.roll(1, -1)) * (0.5 / float(dx))
+
+
+def profile_dict(record):
+    """One (12, P) profiles record as a dict in the manner of :meth:`State.diagnostics`:
+    ``energy``, ``enstrophy``, ``psi_mean``, ``zeta_mean`` and ``vort_flux`` hold the two layers'
+    lines as a (2, P) block, ``interface`` and ``heat_flux`` one (P,) line."""
+    return {"energy": record[0:2], "enstrophy": record[2:4], "interface": record[4], "psi_mean": record[5:7],
+            "zeta_mean": record[7:9], "vort_flux": record[9:11], "heat_flux": record[11]}
 
 
 SPECTRA_LINES = ("energy_1", "energy_2", "enstrophy_1", "enstrophy_2", "interface")

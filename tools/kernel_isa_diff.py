@@ -37,7 +37,9 @@ qg_stencil.hip (untouched) 22 identical.  With the generic and the split passes 
 their own, the four generic kernels differed in the order of two scalar adds in the direct
 DFT's loop (the families share dft_at); they share qg_spec_gen.hip for that reason.  The zonal
 spectra (qg_mi355_spectra.h) left all 190 functions of the sixteen earlier files identical and
-added the 20 of qg_spectra.hip (profiles/spectra/).
+added the 20 of qg_spectra.hip (profiles/spectra/).  The profiles per latitude
+(qg_mi355_profiles.h) left all 210 functions of the seventeen earlier files identical and added
+the 12 of qg_profiles.hip (profiles/meridional/).
 """
 import re
 import sys
