@@ -54,6 +54,9 @@ __global__ __launch_bounds__(Geo<N>::T, Geo<N>::MINW) void spec_passA(SpecArgs a
     // one 8-byte load per line (the coefficient tables do not fit in L1 and are re-read from
     // L2 every row: r01 measured ~18 us of pass A in those reloads with (r, 1/r) + cs).
     // Slot (0, t = 0): .x = k 0, .y = k N/2.
+    // (bw is accumulated with explicit fma: left to contraction, the single context's and the
+    // ensemble's instantiations fused different updates at N >= 256 -- one rounding apart, seen
+    // from the second row of a chunk on -- and a member was no longer a single context's bits)
     double2 u[KQ][2], bw[KQ][2], om[KQ][2];
 #pragma unroll
     for (int q = 0; q < KQ; ++q)
@@ -197,7 +200,7 @@ __global__ __launch_bounds__(Geo<N>::T, Geo<N>::MINW) void spec_passA(SpecArgs a
                             st_u(Urow + s * KS, Store<S>::c(make_double2(u[q][s].x, 0)));
                             st_u(Urow + s * KS + NH, Store<S>::c(make_double2(u[q][s].y, 0)));
                         }
-                        bw[q][s] = make_double2(om[q][s].x * u[q][s].x + bw[q][s].x, om[q][s].y * u[q][s].y + bw[q][s].y);
+                        bw[q][s] = make_double2(fma(om[q][s].x, u[q][s].x, bw[q][s].x), fma(om[q][s].y, u[q][s].y, bw[q][s].y));
                         om[q][s] = make_double2(om[q][s].x * r0, om[q][s].y * rN);
                     }
                 } else {
@@ -211,7 +214,7 @@ __global__ __launch_bounds__(Geo<N>::T, Geo<N>::MINW) void spec_passA(SpecArgs a
                         (void)o;
                         u[q][s] = cfma(r, u[q][s], cscale(B[s], r * csch));
                         st_u(Urow + s * KS + (LX ? t + q * T : k), Store<S>::c(u[q][s]));
-                        bw[q][s] = cfma(om[q][s].x, u[q][s], bw[q][s]);
+                        bw[q][s] = make_double2(fma(om[q][s].x, u[q][s].x, bw[q][s].x), fma(om[q][s].x, u[q][s].y, bw[q][s].y));
                         om[q][s].x *= r;
                     }
                 }

@@ -253,7 +253,7 @@ def get_poisson_cholesky(M, P, dx):  # laplacian.jl:66-75
     return _Factor(_pin_first(-construct_spA(M, P, dx, 0.0)))
 
 
-def solve_longdouble(M, P, dx, alpha, f, pinned=False, workers=None):
+def solve_longdouble(M, P, dx, alpha, f, pinned=False, workers=None, dtype=np.longdouble):
     """Extended-precision reference solve (x86 80-bit long double, eps = 5.4e-20) of the same
     systems: construct_spA(M, P, dx, alpha) x = f over the interior of the (M+2, P+2) field f
     (laplacian.jl:54-58, M, P >= 3), or with ``pinned`` the pinned Poisson system of
@@ -263,9 +263,11 @@ def solve_longdouble(M, P, dx, alpha, f, pinned=False, workers=None):
     scipy.fft in long double, eigenvalues -4 dx^-2 (sin^2(pi kx / M) + sin^2(pi ky / P)) +
     alpha in the cancellation-free form.  Not an F64 solver: it measures how far each F64
     solver (the C oracle, the device) is from the exact solution of the F64 input, so that
-    the difference between two of them can be attributed."""
+    the difference between two of them can be attributed.  ``dtype=np.float64`` runs the same
+    formula in double precision: then it is an F64 solver, a yardstick for the roundoff any of
+    them has at a shape."""
     import scipy.fft as sfft
-    ld = np.longdouble
+    ld = np.dtype(dtype).type
     g = np.asarray(f, dtype=np.float64)[1:-1, 1:-1].astype(ld)
     if pinned:
         g[0, 0] -= np.sum(g)  # (pairwise summation in long double)

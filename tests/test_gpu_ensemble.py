@@ -75,7 +75,14 @@ def check_members(torch, qg, m, B, steps, members, **kw):
 
 
 @pytest.mark.parametrize("M,P,B,steps,chunk", [(8, 3, 2, 5, 0), (64, 48, 5, 5, 8), (256, 16, 3, 4, 0),
-                                               (2048, 8, 2, 3, 0), (128, 128, 16, 4, 0)])
+                                               (2048, 8, 2, 3, 0), (128, 128, 16, 4, 0),
+                                               # (tests/spec_geometry.py: the streaming carry with
+                                               # a member dimension, rows 2, 3, 4 and 64 per chunk)
+                                               (8, 260, 2, 2, 0), (128, 12, 3, 3, 4), (2048, 6, 2, 2, 3),
+                                               (16, 128, 2, 2, 64),
+                                               # (from 128 on the two instantiations of pass A once
+                                               # contracted the chunk summary differently)
+                                               (256, 6, 2, 2, 3), (512, 6, 2, 2, 2), (1024, 6, 2, 2, 3)])
 def test_members_equal_single_contexts_bitwise(env, M, P, B, steps, chunk):
     torch, qg = env
     check_members(torch, qg, qg.bench_model(M, P=P), B, steps, range(B), chunk_rows=chunk)

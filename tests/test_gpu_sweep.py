@@ -77,7 +77,10 @@ def check_sweep(qg, m, members, steps, compare=None, **kw):
 
 
 @pytest.mark.parametrize("M,P,B,steps,chunk", [(8, 3, 3, 5, 0), (64, 48, 5, 5, 8), (256, 16, 3, 4, 0),
-                                               (2048, 8, 2, 3, 0)])
+                                               (2048, 8, 2, 3, 0),
+                                               # (the streaming carry, four rows per chunk)
+                                               (8, 260, 2, 2, 0), (128, 12, 3, 3, 4),
+                                               (2048, 6, 2, 2, 3)])
 def test_all_seven_values_vary(env, M, P, B, steps, chunk):
     """Smallest grid, several chunks, the largest in-LDS row; five steps cover both Euler steps
     and AB3."""
