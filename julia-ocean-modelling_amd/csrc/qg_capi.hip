@@ -13,6 +13,7 @@
 #include "qg_common.hpp"
 #include "qg_mi355_profiles.h"
 #include "qg_mi355_spectra.h"
+#include "qg_mi355_spectra2d.h"
 #include "qg_pcg.hpp"
 #include "qg_spectral.hpp"
 
@@ -43,6 +44,12 @@ size_t spectra_scratch_doubles(int64_t M, int64_t P, int nmembers);
 int launch_spectra_twiddles(double *scratch, int64_t M, hipStream_t s);
 int launch_spectra(const void *z, const void *p, int esize, size_t F, int64_t M, int64_t P, double dx, size_t stride,
                    int nmembers, double *scratch, double *out, hipStream_t s);
+// qg_spectra2d.hip
+bool spectra2d_supports(int64_t M, int64_t P);
+size_t spectra2d_scratch_doubles(int64_t M, int64_t P, int nmembers);
+int launch_spectra2d_twiddles(double *scratch, int64_t M, int64_t P, hipStream_t s);
+int launch_spectra2d(const void *z, const void *p, int esize, size_t F, int64_t M, int64_t P, double dx,
+                     size_t stride, int nmembers, double *scratch, double *out2d, double *iso, hipStream_t s);
 // qg_profiles.hip
 bool profiles_supports(int64_t M, int64_t P);
 int launch_profiles(const void *z, const void *p, int esize, size_t F, int64_t M, int64_t P, double dx, size_t stride,
@@ -125,6 +132,7 @@ struct qg_ctx {
     double *diag = nullptr;  // diagnostics scratch: partial records | record | gathered records
     size_t diag_cap = 0;
     double *spectra = nullptr;  // qg_spectra's scratch: twiddles | partial records (on first use)
+    double *spectra2d = nullptr;  // qg_spectra2d's: twiddles | half-spectra | 2-D record (on first use)
     std::unique_ptr<SpectralSolver> spec;
     std::unique_ptr<PcgSolver> pcg;
     int last_status = QG_OK;  // of the last solve (PCG: QG_ERR_NOT_CONVERGED is kept here)
@@ -304,6 +312,7 @@ int qg_destroy(qg_ctx *c) {
     if (c->ov_halo) (void)hipEventDestroy(c->ov_halo);
     if (c->diag) (void)hipFree(c->diag);
     if (c->spectra) (void)hipFree(c->spectra);
+    if (c->spectra2d) (void)hipFree(c->spectra2d);
     if (c->wind) (void)hipFree(c->wind);
     drop_graphs(c);
     if (c->gstream) (void)hipStreamDestroy(c->gstream);
@@ -1293,6 +1302,51 @@ int qg_run_profiles(qg_ctx *c, int64_t first_step, int64_t nsteps, int64_t every
     for (int64_t t = first_step; t < first_step + nsteps; ++t) {
         QG_CHECK(qg_step(c, t));
         if ((t - first_step + 1) % every == 0) QG_CHECK(profiles_record(c, records + len * (size_t)k++));
+    }
+    return poll_pcg(c, true);  // as qg_run: a failed deferred certificate is reported by the run
+}
+
+// ---- (kx, ky) and isotropic spectra (include/qg_mi355_spectra2d.h; kernels in qg_spectra2d.hip) ----
+// the refusals that need the handle, in the header's order; then the scratch (on first use)
+static int spectra2d_ready(qg_ctx *c) {
+    if (!c->initialised || !c->zeta) return QG_ERR_NOT_BOUND;
+    if (c->distributed || c->nranks != 1 || !spectra2d_supports(c->p.M, c->p.P)) return QG_ERR_UNSUPPORTED;
+    if (c->spectra2d) return QG_OK;
+    QG_HIP(hipSetDevice(c->device));
+    if (hipMalloc((void **)&c->spectra2d, sizeof(double) * spectra2d_scratch_doubles(c->p.M, c->p.P, 1)) !=
+        hipSuccess) {
+        c->spectra2d = nullptr;
+        (void)hipGetLastError();
+        return QG_ERR_ALLOC;
+    }
+    return launch_spectra2d_twiddles(c->spectra2d, c->p.M, c->p.P, c->stream);
+}
+
+// the records of the newest state (device; either may be null); interior points only
+static int spectra2d_record(qg_ctx *c, double *out2d, double *iso) {
+    return launch_spectra2d(c->fieldv(c->zeta, 0, c->heads[0]), c->fieldv(c->psi, 0, c->heads[1]), (int)c->esize,
+                            c->F, c->p.M, c->p.P, c->p.dx, 0, 1, c->spectra2d, out2d, iso, c->stream);
+}
+
+int qg_spectra2d(qg_ctx *c, double *out2d, double *iso) {
+    if (!c || (!out2d && !iso) || !aligned8(out2d) || !aligned8(iso)) return QG_ERR_INVALID_ARG;
+    QG_CHECK(spectra2d_ready(c));
+    QG_HIP(hipSetDevice(c->device));
+    return spectra2d_record(c, out2d, iso);
+}
+
+int qg_run_iso_spectra(qg_ctx *c, int64_t first_step, int64_t nsteps, int64_t every, double *records,
+                       int64_t capacity, int64_t *nrecords) {
+    if (!c || first_step < 1 || nsteps < 0 || every < 1 || !records || !aligned8(records)) return QG_ERR_INVALID_ARG;
+    const int64_t n = nsteps / every;
+    if (capacity < n) return QG_ERR_INVALID_ARG;
+    QG_CHECK(spectra2d_ready(c));
+    if (nrecords) *nrecords = n;
+    const size_t len = (size_t)QG_SPEC_LINES * (size_t)qg_iso_shells(c->p.M, c->p.P);
+    int64_t k = 0;
+    for (int64_t t = first_step; t < first_step + nsteps; ++t) {
+        QG_CHECK(qg_step(c, t));
+        if ((t - first_step + 1) % every == 0) QG_CHECK(spectra2d_record(c, nullptr, records + len * (size_t)k++));
     }
     return poll_pcg(c, true);  // as qg_run: a failed deferred certificate is reported by the run
 }

@@ -29,6 +29,7 @@
 #include "qg_mi355_ensemble.h"
 #include "qg_mi355_profiles.h"
 #include "qg_mi355_spectra.h"
+#include "qg_mi355_spectra2d.h"
 #include "qg_mi355_stats.h"
 #include "qg_mi355_sweep.h"
 #include "qg_spectral.hpp"
@@ -51,6 +52,12 @@ size_t spectra_scratch_doubles(int64_t M, int64_t P, int nmembers);
 int launch_spectra_twiddles(double *scratch, int64_t M, hipStream_t s);
 int launch_spectra(const void *z, const void *p, int esize, size_t F, int64_t M, int64_t P, double dx, size_t stride,
                    int nmembers, double *scratch, double *out, hipStream_t s);
+// qg_spectra2d.hip
+bool spectra2d_supports(int64_t M, int64_t P);
+size_t spectra2d_scratch_doubles(int64_t M, int64_t P, int nmembers);
+int launch_spectra2d_twiddles(double *scratch, int64_t M, int64_t P, hipStream_t s);
+int launch_spectra2d(const void *z, const void *p, int esize, size_t F, int64_t M, int64_t P, double dx,
+                     size_t stride, int nmembers, double *scratch, double *out2d, double *iso, hipStream_t s);
 // qg_profiles.hip
 bool profiles_supports(int64_t M, int64_t P);
 int launch_profiles(const void *z, const void *p, int esize, size_t F, int64_t M, int64_t P, double dx, size_t stride,
@@ -75,6 +82,7 @@ struct qg_ens {
     double *diag = nullptr;    // diagnostics: partial records (reused member after member) | nmembers records
     double *stats = nullptr;   // cross-member statistics: partial sums | one record (on first use)
     double *spectra = nullptr; // zonal spectra: twiddles | every member's partial records (on first use)
+    double *spectra2d = nullptr; // 2-D spectra: twiddles | one batch's half-spectra and 2-D records (on first use)
     SpectralSolver spec;
     size_t F = 0;  // doubles per (M+2, P+2) field
 
@@ -240,6 +248,7 @@ int qg_ens_destroy(qg_ens *e) {
     if (e->diag) (void)hipFree(e->diag);
     if (e->stats) (void)hipFree(e->stats);
     if (e->spectra) (void)hipFree(e->spectra);
+    if (e->spectra2d) (void)hipFree(e->spectra2d);
     delete e;
     return QG_OK;
 }
@@ -532,6 +541,53 @@ int qg_ens_run_profiles(qg_ens *e, int64_t first_step, int64_t nsteps, int64_t e
     for (int64_t t = first_step; t < first_step + nsteps; ++t) {
         QG_CHECK(qg_ens_step(e, t));
         if ((t - first_step + 1) % every == 0) QG_CHECK(ens_profiles_record(e, records + len * (size_t)k++));
+    }
+    return QG_OK;
+}
+
+// ---- (kx, ky) and isotropic spectra (include/qg_mi355_spectra2d.h; kernels in qg_spectra2d.hip) ----
+static int ens_spectra2d_ready(qg_ens *e) {
+    if (!e->zeta) return QG_ERR_NOT_BOUND;
+    if (!spectra2d_supports(e->p.M, e->p.P)) return QG_ERR_UNSUPPORTED;
+    if (e->spectra2d) return QG_OK;
+    QG_HIP(hipSetDevice(e->device));
+    if (hipMalloc((void **)&e->spectra2d,
+                  sizeof(double) * spectra2d_scratch_doubles(e->p.M, e->p.P, e->nmembers)) != hipSuccess) {
+        e->spectra2d = nullptr;
+        (void)hipGetLastError();
+        return QG_ERR_ALLOC;
+    }
+    return launch_spectra2d_twiddles(e->spectra2d, e->p.M, e->p.P, e->stream);
+}
+
+// every member's records of the newest state (device; either may be null): a single context's
+// launches with the member as the grid's second dimension, batch after batch
+static int ens_spectra2d_record(qg_ens *e, double *out2d, double *iso) {
+    return launch_spectra2d(e->field(e->zeta, 0, e->heads[0]), e->field(e->psi, 0, e->heads[1]), (int)sizeof(double),
+                            e->F, e->p.M, e->p.P, e->p.dx, e->member_stride(), e->nmembers, e->spectra2d, out2d, iso,
+                            e->stream);
+}
+
+int qg_ens_spectra2d(qg_ens *e, double *out2d, double *iso) {
+    if (!e || (!out2d && !iso) || !aligned8(out2d) || !aligned8(iso)) return QG_ERR_INVALID_ARG;
+    QG_CHECK(ens_spectra2d_ready(e));
+    QG_HIP(hipSetDevice(e->device));
+    return ens_spectra2d_record(e, out2d, iso);
+}
+
+int qg_ens_run_iso_spectra(qg_ens *e, int64_t first_step, int64_t nsteps, int64_t every, double *records,
+                           int64_t capacity, int64_t *nrecords) {
+    if (!e || first_step < 1 || nsteps < 0 || every < 1 || !records || !aligned8(records)) return QG_ERR_INVALID_ARG;
+    const int64_t n = nsteps / every;
+    if (capacity < n) return QG_ERR_INVALID_ARG;
+    QG_CHECK(ens_spectra2d_ready(e));
+    if (nrecords) *nrecords = n;
+    const size_t len = (size_t)e->nmembers * QG_SPEC_LINES * (size_t)qg_iso_shells(e->p.M, e->p.P);
+    int64_t k = 0;
+    for (int64_t t = first_step; t < first_step + nsteps; ++t) {
+        QG_CHECK(qg_ens_step(e, t));
+        if ((t - first_step + 1) % every == 0)
+            QG_CHECK(ens_spectra2d_record(e, nullptr, records + len * (size_t)k++));
     }
     return QG_OK;
 }

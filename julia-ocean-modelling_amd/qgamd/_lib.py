@@ -162,6 +162,14 @@ SIGNATURES = [
     ("qg_run_profiles", C.c_int, [_vp, _i64, _i64, _i64, _dp, _i64, C.POINTER(_i64)]),
     ("qg_ens_profiles", C.c_int, [_vp, _dp]),
     ("qg_ens_run_profiles", C.c_int, [_vp, _i64, _i64, _i64, _dp, _i64, C.POINTER(_i64)]),
+    # include/qg_mi355_spectra2d.h (the qg_iso_* are host functions; outputs and records: device pointers)
+    ("qg_iso_shells", C.c_int, [_i64, _i64]),
+    ("qg_iso_shell_of", C.c_int, [_i64, _i64, _i64, _i64]),
+    ("qg_iso_shell_counts", C.c_int, [_i64, _i64, C.POINTER(_i64)]),
+    ("qg_spectra2d", C.c_int, [_vp, _dp, _dp]),
+    ("qg_run_iso_spectra", C.c_int, [_vp, _i64, _i64, _i64, _dp, _i64, C.POINTER(_i64)]),
+    ("qg_ens_spectra2d", C.c_int, [_vp, _dp, _dp]),
+    ("qg_ens_run_iso_spectra", C.c_int, [_vp, _i64, _i64, _i64, _dp, _i64, C.POINTER(_i64)]),
 ]
 
 _lib = None

@@ -385,6 +385,26 @@ class State:
         return _run_spectra("qg_run_spectra", self._ctx, self.device, self.zeta.device,
                             (_lib.QG_SPEC_LINES, self.model.M // 2 + 1), first_step, nsteps, every)
 
+    # -- (kx, ky) and isotropic spectra (include/qg_mi355_spectra2d.h) --------------------
+    def spectra2d(self, full=False):
+        """qg_spectra2d: the isotropic spectrum of the newest state as a (5, NK) float64 device
+        tensor -- rows in the order of :data:`ISO_LINES`, column n the shell of total wavenumber
+        :func:`iso_wavenumbers` (M, P, dx)[0][n]; each row sums over n to the field of the same
+        name of :meth:`diagnostics`.  ``full=True`` returns ``(full2d, iso)`` with the (5, P,
+        M/2+1) spectrum over (ky, kx) it is folded from (the layout of an rfft2 over (y, x));
+        iso is bit for bit the same either way.  Enqueued on the current stream, not
+        synchronised.  One rank, M and P powers of two in 8..2048."""
+        return _spectra2d("qg_spectra2d", self._ctx, self.device, self.zeta.device, (), self.model, full)
+
+    def run_iso_spectra(self, first_step, nsteps, every):
+        """qg_run_iso_spectra: :meth:`run` (stepped on the stream) that records the isotropic
+        spectrum of :meth:`spectra2d` after every ``every``-th step on the device, without a host
+        round trip.  Returns the (nsteps // every, 5, NK) float64 device tensor of records.  Not
+        synchronised."""
+        self._need_transport()
+        return _run_spectra("qg_run_iso_spectra", self._ctx, self.device, self.zeta.device,
+                            (_lib.QG_SPEC_LINES, iso_shells(self.model.M, self.model.P)), first_step, nsteps, every)
+
     # -- zonal-mean profiles per latitude (include/qg_mi355_profiles.h) -----------------
     def profiles(self):
         """qg_profiles: the per-latitude lines of the newest state as a (12, P) float64 device
@@ -816,6 +836,24 @@ class Ensemble:
         return _run_spectra("qg_ens_run_spectra", self._ens, self.device, self.zeta.device,
                             (self.nmembers, _lib.QG_SPEC_LINES, self.model.M // 2 + 1), first_step, nsteps, every)
 
+    # ---- (kx, ky) and isotropic spectra (include/qg_mi355_spectra2d.h) ----
+    def spectra2d(self, full=False):
+        """qg_ens_spectra2d: every member's isotropic spectrum of the newest state as a
+        (B, 5, NK) float64 device tensor, or with ``full=True`` ``(full2d, iso)`` with the
+        (B, 5, P, M/2+1) spectra over (ky, kx); member b's blocks are bit for bit
+        :meth:`State.spectra2d` of a State holding member b's arrays.  Three launches per batch
+        of members on the current stream, not synchronised."""
+        return _spectra2d("qg_ens_spectra2d", self._ens, self.device, self.zeta.device, (self.nmembers,),
+                          self.model, full)
+
+    def run_iso_spectra(self, first_step, nsteps, every):
+        """qg_ens_run_iso_spectra: :meth:`run` that records the isotropic spectra of
+        :meth:`spectra2d` after every ``every``-th step on the device, without a host round trip.
+        Returns the (nsteps // every, B, 5, NK) float64 device tensor of records.  Not
+        synchronised."""
+        return _run_spectra("qg_ens_run_iso_spectra", self._ens, self.device, self.zeta.device,
+                            (self.nmembers, _lib.QG_SPEC_LINES, iso_shells(self.model.M, self.model.P)),
+                            first_step, nsteps, every)
 
     # ---- zonal-mean profiles per latitude (include/qg_mi355_profiles.h) ----
     def profiles(self):
@@ -884,6 +922,41 @@ SPECTRA_STRIP_CAP = _lib.QG_SPEC_MAX_STRIPS
 def spectra_wavenumbers(M, dx):
     """The zonal wavenumbers 2 pi k / (M dx), k = 0 .. M/2, of the columns of a spectra record."""
     return 2.0 * np.pi * np.arange(int(M) // 2 + 1) / (int(M) * float(dx))
+
+
+ISO_LINES = SPECTRA_LINES
+"""The rows of an isotropic or (kx, ky) spectrum (include/qg_mi355_spectra2d.h): those of
+:data:`SPECTRA_LINES`, with the same sums."""
+
+
+def iso_shells(M, P):
+    """qg_iso_shells: the number NK of shells of an (M, P) grid (a host function: no device)."""
+    nk = _lib.lib().qg_iso_shells(int(M), int(P))
+    if nk < 0:
+        raise _lib.QGError("qg_iso_shells", nk)
+    return nk
+
+
+def iso_wavenumbers(M, P, dx):
+    """``(k, counts)`` of the columns of an isotropic spectrum: the shell centres
+    k[n] = 2 pi n / (max(M, P) dx) in rad/m, and per shell the number of full-plane (kx, ky) cells
+    it holds (qg_iso_shell_counts; they sum to M P) for normalising to a density."""
+    nk = iso_shells(M, P)
+    counts = (C.c_int64 * nk)()
+    call("qg_iso_shell_counts", int(M), int(P), counts)
+    return (2.0 * np.pi * np.arange(nk) / (max(int(M), int(P)) * float(dx)),
+            np.frombuffer(counts, dtype=np.int64).copy())
+
+
+def _spectra2d(name, handle, device, tdev, lead, model, full):
+    torch = _torch()
+    M, P = int(model.M), int(model.P)
+    iso = torch.empty(tuple(lead) + (_lib.QG_SPEC_LINES, iso_shells(M, P)), dtype=torch.float64, device=tdev)
+    out = torch.empty(tuple(lead) + (_lib.QG_SPEC_LINES, P, M // 2 + 1), dtype=torch.float64,
+                      device=tdev) if full else None
+    with torch.cuda.device(device):
+        call(name, handle, _ptr(out) if full else None, _ptr(iso))
+    return (out, iso) if full else iso
 
 
 def _run_spectra(name, handle, device, tdev, shape, first_step, nsteps, every):

@@ -39,7 +39,9 @@ DFT's loop (the families share dft_at); they share qg_spec_gen.hip for that reas
 spectra (qg_mi355_spectra.h) left all 190 functions of the sixteen earlier files identical and
 added the 20 of qg_spectra.hip (profiles/spectra/).  The profiles per latitude
 (qg_mi355_profiles.h) left all 210 functions of the seventeen earlier files identical and added
-the 12 of qg_profiles.hip (profiles/meridional/).
+the 12 of qg_profiles.hip (profiles/meridional/).  The 2-D and isotropic spectra
+(qg_mi355_spectra2d.h) left all 222 functions of the eighteen earlier files identical and added
+the 28 of qg_spectra2d.hip (profiles/spectra2d/isa_diff.txt).
 """
 import re
 import sys
