@@ -16,6 +16,7 @@
 #include "qg_mi355_spectra2d.h"
 #include "qg_pcg.hpp"
 #include "qg_spectral.hpp"
+#include "qg_tracer.hpp"
 
 namespace qg {
 static std::atomic<int> g_form[QG_FORM_COUNT];  // qg_set_form (zero-initialised: automatic)
@@ -148,6 +149,23 @@ struct qg_ctx {
     T *fieldt(void *base, int layer, int slot) const { return static_cast<T *>(fieldv(base, layer, slot)); }
     int64_t row_words() const { return (int64_t)((p.M + 2) * esize / 8); }  // a row, in 8-byte words
 };
+
+// the owner's side of the tracer handles (qg_tracer.hpp): host only
+void qg::tracer_owner(const qg_ctx *c, TracerOwner *o) {
+    *o = TracerOwner{};
+    o->M = c->p.M;
+    o->P = c->p.P;
+    o->dx = c->p.dx;
+    o->dt = c->p.dt;
+    o->U = c->p.U;
+    o->device = c->device;
+    o->stream = c->stream;
+    o->F = c->F;
+    o->bound = c->initialised && c->zeta;
+    o->supported = c->esize == sizeof(double) && !c->distributed && c->nranks == 1 && c->p.M >= 3 && c->p.P >= 3;
+    if (o->bound && o->supported)
+        for (int l = 0; l < 2; ++l) o->psi[l] = c->field(c->psi, l, c->heads[1]);
+}
 
 extern "C" {
 

@@ -33,6 +33,7 @@
 #include "qg_mi355_stats.h"
 #include "qg_mi355_sweep.h"
 #include "qg_spectral.hpp"
+#include "qg_tracer.hpp"
 
 namespace qg {
 int diag_record_len();
@@ -79,6 +80,7 @@ struct qg_ens {
     std::vector<qg_member_params> mp;  // the members' own parameters (qg_mi355_sweep.h)
     std::vector<Derived> md;           // derive() of the base with member b's values substituted
     TendMember *rec = nullptr;         // device [nmembers] records: the sweep tendency (else null)
+    bool sweep = false;                // made by qg_ens_create_sweep (the tracer handles refuse it)
     double *diag = nullptr;    // diagnostics: partial records (reused member after member) | nmembers records
     double *stats = nullptr;   // cross-member statistics: partial sums | one record (on first use)
     double *spectra = nullptr; // zonal spectra: twiddles | every member's partial records (on first use)
@@ -89,6 +91,25 @@ struct qg_ens {
     size_t member_stride() const { return 6 * F; }  // doubles between two members' blocks
     double *field(double *base, int layer, int slot) const { return base + F * (size_t)(layer + 2 * slot); }
 };
+
+// the owner's side of the tracer handles (qg_tracer.hpp): host only
+void qg::tracer_owner(const qg_ens *e, TracerOwner *o) {
+    *o = TracerOwner{};
+    o->M = e->p.M;
+    o->P = e->p.P;
+    o->dx = e->p.dx;
+    o->dt = e->p.dt;
+    o->U = e->mp[0].U;
+    o->device = e->device;
+    o->stream = e->stream;
+    o->nmembers = e->nmembers;
+    o->F = e->F;
+    o->member_stride = e->member_stride();
+    o->bound = e->zeta != nullptr;
+    o->supported = !e->sweep && e->p.M >= 3 && e->p.P >= 3;  // (per-member U is left for later)
+    if (o->bound && o->supported)
+        for (int l = 0; l < 2; ++l) o->psi[l] = e->field(e->psi, l, e->heads[1]);
+}
 
 // the base parameters with member m's seven values substituted
 static qg_params member_qg_params(const qg_params &p, const qg_member_params &m) {
@@ -139,6 +160,7 @@ static int ens_create(const qg_params *p, const qg_member_params *mp, int nmembe
     e->device = device;
     e->stream = static_cast<hipStream_t>(stream);
     e->nmembers = nmembers;
+    e->sweep = mp != nullptr;
     e->F = (size_t)(p->M + 2) * (size_t)(p->P + 2);
     e->mp.assign((size_t)nmembers, base_member_params(*p));
     if (mp) std::memcpy(e->mp.data(), mp, sizeof(qg_member_params) * (size_t)nmembers);

@@ -18,6 +18,15 @@ QG_ERR_ALLOC, QG_ERR_RCCL, QG_ERR_NOT_CONVERGED = -5, -6, -7
 QG_ENS_MAX_MEMBERS = 65535
 QG_SPEC_LINES, QG_SPEC_MAX_STRIPS = 5, 64
 QG_PROF_LINES = 12
+QG_TRACERS_MAX, QG_TRC_LINES = 8, 6
+QG_TRC_FORM_AUTO, QG_TRC_FORM_RING, QG_TRC_FORM_ONE_POINT = 0, 1, 2
+
+
+def QG_TRC_FORM_RING_TILE(w, r):
+    """The ring form with strips w columns wide (64, 128, 256) and r rows per workgroup."""
+    return (int(w) << 16) | (int(r) << 4) | QG_TRC_FORM_RING
+
+
 QG_XBUF_TO_NEXT, QG_XBUF_TO_PREV, QG_XBUF_FROM_PREV, QG_XBUF_FROM_NEXT = 0, 1, 2, 3
 QG_SOLVER_SPECTRAL = 0
 QG_F64, QG_F32 = 0, 1
@@ -70,6 +79,13 @@ class QgSpread(C.Structure):
                 ("psi_mean_sq", C.c_double * 2), ("energy_spread", C.c_double * 2),
                 ("energy_mean", C.c_double * 2), ("step", C.c_double), ("nmembers", C.c_double),
                 ("reserved", C.c_double * 2)]
+
+
+class QgTracerParams(C.Structure):
+    """Mirror of ``struct qg_tracer_params`` (include/qg_mi355_tracers.h): one tracer's layer (0 or
+    1), diffusivity and imposed mean meridional gradient."""
+
+    _fields_ = [("layer", C.c_int32), ("reserved", C.c_int32), ("kappa", C.c_double), ("gamma", C.c_double)]
 
 
 class QgStats(C.Structure):
@@ -170,6 +186,20 @@ SIGNATURES = [
     ("qg_run_iso_spectra", C.c_int, [_vp, _i64, _i64, _i64, _dp, _i64, C.POINTER(_i64)]),
     ("qg_ens_spectra2d", C.c_int, [_vp, _dp, _dp]),
     ("qg_ens_run_iso_spectra", C.c_int, [_vp, _i64, _i64, _i64, _dp, _i64, C.POINTER(_i64)]),
+    # include/qg_mi355_tracers.h (arrays, outputs and records: device pointers)
+    ("qg_tracers_create", C.c_int, [_vp, C.c_int, C.POINTER(QgTracerParams), C.POINTER(_vp)]),
+    ("qg_ens_tracers_create", C.c_int, [_vp, C.c_int, C.POINTER(QgTracerParams), C.POINTER(_vp)]),
+    ("qg_tracers_destroy", C.c_int, [_vp]),
+    ("qg_tracers_bind", C.c_int, [_vp, _dp, _dp]),
+    ("qg_tracers_reset", C.c_int, [_vp]),
+    ("qg_tracers_advance", C.c_int, [_vp]),
+    ("qg_tracers_step", C.c_int, [_vp, _i64]),
+    ("qg_tracers_run", C.c_int, [_vp, _i64, _i64, _i64, _dp, _i64, C.POINTER(_i64)]),
+    ("qg_tracers_diagnostics", C.c_int, [_vp, _dp]),
+    ("qg_tracers_slot", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    ("qg_tracers_get_state", C.c_int, [_vp, C.POINTER(_i64), C.POINTER(C.c_int)]),
+    ("qg_tracers_set_state", C.c_int, [_vp, _i64, C.POINTER(C.c_int)]),
+    ("qg_tracers_set_form", C.c_int, [_vp, C.c_int]),
 ]
 
 _lib = None

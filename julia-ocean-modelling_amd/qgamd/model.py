@@ -876,6 +876,169 @@ class Ensemble:
                             (self.nmembers, _lib.QG_PROF_LINES, self.model.P), first_step, nsteps, every)
 
 
+class Tracers:
+    """Passive tracers advected by the layer flow of a :class:`State` or an :class:`Ensemble`
+    (include/qg_mi355_tracers.h): tracer k lives in layer ``layers[k]`` (0 or 1), has the
+    diffusivity ``kappa[k]`` >= 0 and the imposed mean meridional gradient ``gamma[k]``,
+
+      G_k = ((kappa_k laplace_5p(c_k) - J(dx, c_k, psi_l)) - U_l cd(c_k)) - gamma_k cd(psi_l)
+
+    stepped by the reference's Euler / AB3 update on its own history, bit for bit the numpy
+    expression on the owner's newest psi.  The owner is never changed.
+
+    ``c`` and ``g_store`` are (3, NT, P+2, M+2) float64 tensors -- (B, 3, NT, P+2, M+2) for an
+    Ensemble -- whose slots rotate: :meth:`slot` names the physical slot of logical slot 1 (the
+    newest), :meth:`current` returns the newest field.  Fill slot 0 (:meth:`set`) and call
+    :meth:`reset` before the first advance.  F64, one rank, M and P >= 3, no sweep ensembles
+    (QGError with QG_ERR_UNSUPPORTED otherwise).  Close it before its owner."""
+
+    def __init__(self, owner, layers, kappa=None, gamma=None):
+        torch = _torch()
+        layers = [int(v) for v in layers]
+        nt = len(layers)
+        kappa = [0.0] * nt if kappa is None else [float(v) for v in kappa]
+        gamma = [0.0] * nt if gamma is None else [float(v) for v in gamma]
+        if len(kappa) != nt or len(gamma) != nt:
+            raise ValueError(f"{nt} layers, {len(kappa)} kappa, {len(gamma)} gamma: one of each per tracer")
+        self.owner = owner
+        self.ntracers = nt
+        self.layers, self.kappa, self.gamma = layers, kappa, gamma
+        self.device = owner.device
+        self.nmembers = getattr(owner, "nmembers", None)
+        m = owner.model
+        tp = (_lib.QgTracerParams * max(nt, 1))()
+        for k in range(nt):
+            tp[k].layer, tp[k].reserved, tp[k].kappa, tp[k].gamma = layers[k], 0, kappa[k], gamma[k]
+        self._trc = C.c_void_p()
+        with torch.cuda.device(self.device):
+            # created first: an unsupported owner is refused before anything is allocated
+            if self.nmembers is None:
+                call("qg_tracers_create", owner._ctx, nt, tp, C.byref(self._trc))
+            else:
+                call("qg_ens_tracers_create", owner._ens, nt, tp, C.byref(self._trc))
+            shape = (3, nt, m.P + 2, m.M + 2)
+            if self.nmembers is not None:
+                shape = (self.nmembers,) + shape
+            self.c = torch.zeros(shape, dtype=torch.float64, device=owner.psi.device)
+            self.g_store = torch.zeros(shape, dtype=torch.float64, device=owner.psi.device)
+            call("qg_tracers_bind", self._trc, _ptr(self.c), _ptr(self.g_store))
+
+    def close(self):
+        """Destroy the library handle now (qg_tracers_destroy); the tensors stay with the caller."""
+        trc = getattr(self, "_trc", None)
+        if trc and _lib._lib is not None:
+            _lib._lib.qg_tracers_destroy(trc)
+            self._trc = None
+
+    def __del__(self):
+        self.close()
+
+    def bind(self, c, g_store):
+        """qg_tracers_bind: other arrays of the same shape (the caller keeps them alive); follow
+        with :meth:`reset` or :meth:`set_state`."""
+        for t in (c, g_store):
+            if tuple(t.shape) != tuple(self.c.shape) or t.dtype != self.c.dtype or not t.is_contiguous():
+                raise ValueError(f"expected contiguous float64 tensors of shape {tuple(self.c.shape)}")
+        call("qg_tracers_bind", self._trc, _ptr(c), _ptr(g_store))
+        self.c, self.g_store = c, g_store
+
+    def set(self, k, field):
+        """Tracer k's initial interior: ``field`` is (P, M) -- (B, P, M) or (P, M) for every member
+        of an Ensemble -- written into slot 0; :meth:`reset` then fills the ghost ring."""
+        torch = _torch()
+        f = torch.as_tensor(field, dtype=torch.float64, device=self.c.device)
+        self.c[..., 0, int(k), 1:-1, 1:-1] = f
+
+    def reset(self):
+        """qg_tracers_reset: slot 0 of ``c`` becomes the initial tracers (ghost ring filled from
+        the interior), everything else zero, age 0."""
+        with _torch().cuda.device(self.device):
+            call("qg_tracers_reset", self._trc)
+        return self
+
+    def advance(self):
+        """qg_tracers_advance: one tracer step with the owner's newest psi; the owner is not
+        touched.  Call it before the owner's step of the same timestep."""
+        with _torch().cuda.device(self.device):
+            call("qg_tracers_advance", self._trc)
+
+    def step(self, timestep):
+        """qg_tracers_step: :meth:`advance`, then the owner's step."""
+        with _torch().cuda.device(self.device):
+            call("qg_tracers_step", self._trc, int(timestep))
+
+    def run(self, first_step, nsteps, every=None):
+        """qg_tracers_run: ``nsteps`` of :meth:`step`.  With ``every=k`` the diagnostics record is
+        taken on the device after every k-th step: returns the (nsteps // k, [B,] NT, 6) float64
+        device tensor of records (see :data:`TRACER_LINES`).  Not synchronised."""
+        torch = _torch()
+        if every is None:
+            with torch.cuda.device(self.device):
+                call("qg_tracers_run", self._trc, int(first_step), int(nsteps), 1, None, 0, None)
+            return None
+        lead = () if self.nmembers is None else (self.nmembers,)
+        return _run_spectra("qg_tracers_run", self._trc, self.device, self.c.device,
+                            lead + (self.ntracers, _lib.QG_TRC_LINES), first_step, nsteps, every)
+
+    def diagnostics(self):
+        """qg_tracers_diagnostics: the ([B,] NT, 6) float64 device tensor of the newest tracers'
+        records, columns in the order of :data:`TRACER_LINES`.  Not synchronised."""
+        torch = _torch()
+        lead = () if self.nmembers is None else (self.nmembers,)
+        out = torch.empty(lead + (self.ntracers, _lib.QG_TRC_LINES), dtype=torch.float64, device=self.c.device)
+        with torch.cuda.device(self.device):
+            call("qg_tracers_diagnostics", self._trc, _ptr(out))
+        return out
+
+    def slot(self, which, logical):
+        w = {"c": 0, "g_store": 1}[which]
+        out = C.c_int()
+        call("qg_tracers_slot", self._trc, w, int(logical), C.byref(out))
+        return out.value
+
+    def current(self, k):
+        """The newest field of tracer k: a (P+2, M+2) view, (B, P+2, M+2) for an Ensemble."""
+        return self.c[..., self.slot("c", 1), int(k), :, :]
+
+    def state(self):
+        """qg_tracers_get_state: ``(age, [head_c, head_g_store])`` for a checkpoint beside the
+        two tensors."""
+        age, heads = C.c_int64(), (C.c_int * 2)()
+        call("qg_tracers_get_state", self._trc, C.byref(age), heads)
+        return age.value, list(heads)
+
+    def set_state(self, age, heads):
+        """qg_tracers_set_state: resume from :meth:`state` with the tensors' contents restored."""
+        call("qg_tracers_set_state", self._trc, int(age), (C.c_int * 2)(*[int(h) for h in heads]))
+
+    def set_form(self, form):
+        """qg_tracers_set_form: ``_lib.QG_TRC_FORM_*`` (0: chosen by size)."""
+        call("qg_tracers_set_form", self._trc, int(form))
+
+
+TRACER_LINES = ("sum", "variance", "min", "max", "flux_v", "grad2")
+"""The columns of a tracer diagnostics record, interior points only, indices wrapping:
+dx^2 sum c; 1/2 dx^2 sum c^2; min; max; (1/(M P)) sum v_l c with v_l = cd(psi_l); and
+1/2 sum (cx^2 + cy^2) of the forward differences."""
+
+
+def tracer_dicts(records):
+    """Records of :meth:`Tracers.diagnostics` or :meth:`Tracers.run` -- (..., 6), any leading
+    dimensions -- as a dict of (...) blocks keyed by :data:`TRACER_LINES`."""
+    return {name: records[..., q] for q, name in enumerate(TRACER_LINES)}
+
+
+def eddy_diffusivity(records, gamma):
+    """K = -flux_v / Gamma per tracer from records (..., NT, 6) and the NT gradients: (..., NT)
+    of the records' kind (infinite or nan where Gamma is 0)."""
+    flux = records[..., 4]
+    if isinstance(flux, np.ndarray):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return -flux / np.asarray(gamma, dtype=np.float64)
+    torch = _torch()
+    return -flux / torch.as_tensor(gamma, dtype=torch.float64, device=flux.device)
+
+
 PROFILE_LINES = ("energy_1", "energy_2", "enstrophy_1", "enstrophy_2", "interface", "psi_mean_1", "psi_mean_2",
                  "zeta_mean_1", "zeta_mean_2", "vort_flux_1", "vort_flux_2", "heat_flux")
 """The rows of a profiles record (layers 1-based, as the reference counts them), each a function
