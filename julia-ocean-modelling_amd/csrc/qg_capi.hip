@@ -164,7 +164,10 @@ void qg::tracer_owner(const qg_ctx *c, TracerOwner *o) {
     o->bound = c->initialised && c->zeta;
     o->supported = c->esize == sizeof(double) && !c->distributed && c->nranks == 1 && c->p.M >= 3 && c->p.P >= 3;
     if (o->bound && o->supported)
-        for (int l = 0; l < 2; ++l) o->psi[l] = c->field(c->psi, l, c->heads[1]);
+        for (int l = 0; l < 2; ++l) {
+            o->psi[l] = c->field(c->psi, l, c->heads[1]);
+            o->zeta[l] = c->field(c->zeta, l, c->heads[0]);
+        }
 }
 
 extern "C" {

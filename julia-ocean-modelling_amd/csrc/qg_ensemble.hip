@@ -108,7 +108,10 @@ void qg::tracer_owner(const qg_ens *e, TracerOwner *o) {
     o->bound = e->zeta != nullptr;
     o->supported = !e->sweep && e->p.M >= 3 && e->p.P >= 3;  // (per-member U is left for later)
     if (o->bound && o->supported)
-        for (int l = 0; l < 2; ++l) o->psi[l] = e->field(e->psi, l, e->heads[1]);
+        for (int l = 0; l < 2; ++l) {
+            o->psi[l] = e->field(e->psi, l, e->heads[1]);
+            o->zeta[l] = e->field(e->zeta, l, e->heads[0]);
+        }
 }
 
 // the base parameters with member m's seven values substituted

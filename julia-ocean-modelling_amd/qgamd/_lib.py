@@ -20,6 +20,8 @@ QG_SPEC_LINES, QG_SPEC_MAX_STRIPS = 5, 64
 QG_PROF_LINES = 12
 QG_TRACERS_MAX, QG_TRC_LINES = 8, 6
 QG_TRC_FORM_AUTO, QG_TRC_FORM_RING, QG_TRC_FORM_ONE_POINT = 0, 1, 2
+QG_FLT_LINES, QG_FLOATS_MAX_PER_LAYER = 8, 1 << 26
+QG_FLT_PSI, QG_FLT_ZETA = 0, 1
 
 
 def QG_TRC_FORM_RING_TILE(w, r):
@@ -200,6 +202,19 @@ SIGNATURES = [
     ("qg_tracers_get_state", C.c_int, [_vp, C.POINTER(_i64), C.POINTER(C.c_int)]),
     ("qg_tracers_set_state", C.c_int, [_vp, _i64, C.POINTER(C.c_int)]),
     ("qg_tracers_set_form", C.c_int, [_vp, C.c_int]),
+    # include/qg_mi355_floats.h (arrays, outputs and records: device pointers)
+    ("qg_floats_create", C.c_int, [_vp, _i64, _i64, C.POINTER(_vp)]),
+    ("qg_ens_floats_create", C.c_int, [_vp, _i64, _i64, C.POINTER(_vp)]),
+    ("qg_floats_destroy", C.c_int, [_vp]),
+    ("qg_floats_bind", C.c_int, [_vp, _dp, _dp, _dp]),
+    ("qg_floats_reset", C.c_int, [_vp]),
+    ("qg_floats_advance", C.c_int, [_vp]),
+    ("qg_floats_step", C.c_int, [_vp, _i64]),
+    ("qg_floats_run", C.c_int, [_vp, _i64, _i64, _i64, _dp, _dp, _i64, C.POINTER(_i64)]),
+    ("qg_floats_stats", C.c_int, [_vp, _dp]),
+    ("qg_floats_sample", C.c_int, [_vp, C.c_int, _dp]),
+    ("qg_floats_get_state", C.c_int, [_vp, C.POINTER(_i64), C.POINTER(C.c_int)]),
+    ("qg_floats_set_state", C.c_int, [_vp, _i64, C.c_int]),
 ]
 
 _lib = None

@@ -1039,6 +1039,171 @@ def eddy_diffusivity(records, gamma):
     return -flux / torch.as_tensor(gamma, dtype=torch.float64, device=flux.device)
 
 
+class Floats:
+    """Lagrangian floats advected by the layer flow of a :class:`State` or an :class:`Ensemble`
+    (include/qg_mi355_floats.h): ``n0`` floats in layer 0, then ``n1`` in layer 1, in every
+    member.  A float's velocity is the bilinear interpolant of the centred-difference node
+    velocities of the owner's newest psi (plus ``U`` in layer 0), stepped by the reference's
+    Euler / AB3 update on its own history, bit for bit the header's contract in numpy.  The
+    owner is never changed.
+
+    ``pos`` and ``origin`` are (2, N) float64 tensors -- (B, 2, N) for an Ensemble -- holding
+    xi (along x, M points) and eta in grid units, unwrapped; ``hist`` is (2, 2, N) -- (B, 2, 2,
+    N) -- with the two previous (u, v) in m/s.  :meth:`seed` and :meth:`reset` before the first
+    advance.  F64, one rank, M and P >= 3, no sweep ensembles (QGError with QG_ERR_UNSUPPORTED
+    otherwise).  Close it before its owner."""
+
+    def __init__(self, owner, n0, n1=0):
+        torch = _torch()
+        self.owner = owner
+        self.n0, self.n1 = int(n0), int(n1)
+        self.nfloats = self.n0 + self.n1
+        self.device = owner.device
+        self.nmembers = getattr(owner, "nmembers", None)
+        self._flt = C.c_void_p()
+        with torch.cuda.device(self.device):
+            # created first: an unsupported owner or count is refused before anything is allocated
+            if self.nmembers is None:
+                call("qg_floats_create", owner._ctx, self.n0, self.n1, C.byref(self._flt))
+            else:
+                call("qg_ens_floats_create", owner._ens, self.n0, self.n1, C.byref(self._flt))
+            lead = () if self.nmembers is None else (self.nmembers,)
+            kw = dict(dtype=torch.float64, device=owner.psi.device)
+            self.pos = torch.zeros(lead + (2, self.nfloats), **kw)
+            self.origin = torch.zeros(lead + (2, self.nfloats), **kw)
+            self.hist = torch.zeros(lead + (2, 2, self.nfloats), **kw)
+            call("qg_floats_bind", self._flt, _ptr(self.pos), _ptr(self.origin), _ptr(self.hist))
+
+    def close(self):
+        """Destroy the library handle now (qg_floats_destroy); the tensors stay with the caller."""
+        flt = getattr(self, "_flt", None)
+        if flt and _lib._lib is not None:
+            _lib._lib.qg_floats_destroy(flt)
+            self._flt = None
+
+    def __del__(self):
+        self.close()
+
+    def _lead(self):
+        return () if self.nmembers is None else (self.nmembers,)
+
+    def bind(self, pos, origin, hist):
+        """qg_floats_bind: other arrays of the same shapes (the caller keeps them alive); follow
+        with :meth:`reset` or :meth:`set_state`."""
+        for t, ref in ((pos, self.pos), (origin, self.origin), (hist, self.hist)):
+            if tuple(t.shape) != tuple(ref.shape) or t.dtype != ref.dtype or not t.is_contiguous():
+                raise ValueError(f"expected a contiguous float64 tensor of shape {tuple(ref.shape)}")
+        call("qg_floats_bind", self._flt, _ptr(pos), _ptr(origin), _ptr(hist))
+        self.pos, self.origin, self.hist = pos, origin, hist
+
+    def seed(self, xi, eta):
+        """The initial positions in grid units: ``xi`` and ``eta`` are (N,) -- or (B, N) -- and
+        go into ``pos``; :meth:`reset` then makes them the origin."""
+        torch = _torch()
+        self.pos[..., 0, :] = torch.as_tensor(xi, dtype=torch.float64, device=self.pos.device)
+        self.pos[..., 1, :] = torch.as_tensor(eta, dtype=torch.float64, device=self.pos.device)
+        return self
+
+    def reset(self):
+        """qg_floats_reset: origin = pos, hist = 0, head = 0, age = 0."""
+        with _torch().cuda.device(self.device):
+            call("qg_floats_reset", self._flt)
+        return self
+
+    def advance(self):
+        """qg_floats_advance: one float step with the owner's newest psi; the owner is not
+        touched.  Call it before the owner's step of the same timestep."""
+        with _torch().cuda.device(self.device):
+            call("qg_floats_advance", self._flt)
+
+    def step(self, timestep):
+        """qg_floats_step: :meth:`advance`, then the owner's step."""
+        with _torch().cuda.device(self.device):
+            call("qg_floats_step", self._flt, int(timestep))
+
+    def run(self, first_step, nsteps, every=None, trajectories=True, stats=True):
+        """qg_floats_run: ``nsteps`` of :meth:`step`.  With ``every=k``, after every k-th step the
+        positions and / or the statistics record are kept on the device: returns
+        ``(traj, records)`` -- (nsteps // k, [B,] 2, N) and (nsteps // k, [B,] 2, 8) float64
+        device tensors, ``None`` for the one switched off.  Not synchronised."""
+        torch = _torch()
+        first_step, nsteps = int(first_step), int(nsteps)
+        if every is None or not (trajectories or stats):
+            with torch.cuda.device(self.device):
+                call("qg_floats_run", self._flt, first_step, nsteps, 1, None, None, 0, None)
+            return None
+        every = int(every)
+        if every < 1:
+            raise ValueError("every must be >= 1")
+        n = max(nsteps, 0) // every
+        kw = dict(dtype=torch.float64, device=self.pos.device)
+        # (an empty tensor has no address: one spare record keeps the pointer non-null)
+        traj = torch.zeros((max(n, 1),) + self._lead() + (2, self.nfloats), **kw) if trajectories else None
+        rec = torch.zeros((max(n, 1),) + self._lead() + (2, _lib.QG_FLT_LINES), **kw) if stats else None
+        got = C.c_int64()
+        with torch.cuda.device(self.device):
+            call("qg_floats_run", self._flt, first_step, nsteps, every, None if traj is None else _ptr(traj),
+                 None if rec is None else _ptr(rec), n, C.byref(got))
+        return (None if traj is None else traj[:got.value], None if rec is None else rec[:got.value])
+
+    def stats(self):
+        """qg_floats_stats: the ([B,] 2, 8) float64 device tensor of the Lagrangian record, one
+        row per layer, columns in the order of :data:`FLOAT_LINES`.  Not synchronised."""
+        torch = _torch()
+        out = torch.empty(self._lead() + (2, _lib.QG_FLT_LINES), dtype=torch.float64, device=self.pos.device)
+        with torch.cuda.device(self.device):
+            call("qg_floats_stats", self._flt, _ptr(out))
+        return out
+
+    def sample(self, field="psi"):
+        """qg_floats_sample: the owner's newest ``"psi"`` or ``"zeta"`` of each float's own layer
+        at its position (the contract's bilinear lines): ([B,] N) float64, on the device."""
+        torch = _torch()
+        f = {"psi": _lib.QG_FLT_PSI, "zeta": _lib.QG_FLT_ZETA}[field]
+        out = torch.empty(self._lead() + (self.nfloats,), dtype=torch.float64, device=self.pos.device)
+        with torch.cuda.device(self.device):
+            call("qg_floats_sample", self._flt, f, _ptr(out))
+        return out
+
+    def state(self):
+        """qg_floats_get_state: ``(age, head)`` for a checkpoint beside the three tensors."""
+        age, head = C.c_int64(), C.c_int()
+        call("qg_floats_get_state", self._flt, C.byref(age), C.byref(head))
+        return age.value, head.value
+
+    def set_state(self, age, head):
+        """qg_floats_set_state: resume from :meth:`state` with the tensors' contents restored."""
+        call("qg_floats_set_state", self._flt, int(age), int(head))
+
+
+FLOAT_LINES = ("n", "mean_dx", "mean_dy", "var_dx", "var_dy", "cov_dxdy", "kinetic", "pair_dispersion")
+"""The columns of a floats record, one row per layer, physical units: the number of floats; the
+mean displacements <Dx>, <Dy> with D = (pos - origin) dx; the second moments <Dx^2>, <Dy^2>,
+<Dx Dy> (about zero, not about the mean); 1/2 <u^2 + v^2> of the newest sampled velocities; and
+<|r_2p - r_2p+1|^2> over the consecutive pairs of the layer's floats."""
+
+
+def float_dicts(records):
+    """Records of :meth:`Floats.stats` or :meth:`Floats.run` -- (..., 8), any leading dimensions
+    -- as a dict of (...) blocks keyed by :data:`FLOAT_LINES`."""
+    return {name: records[..., q] for q, name in enumerate(FLOAT_LINES)}
+
+
+def float_positions(pos, dx, wrap=False):
+    """Positions (..., 2, N) in grid units as metres: x = xi dx, y = eta dx.  ``wrap=(M, P)``
+    folds them into the domain [0, M dx) x [0, P dx) first; the unwrapped ones (``wrap=False``)
+    keep the turns a float has made.  numpy in, numpy out; torch in, torch out."""
+    if not wrap:
+        return pos * dx
+    M, P = wrap
+    floor = np.floor if isinstance(pos, np.ndarray) else (lambda t: t.floor())
+    out = pos.copy() if isinstance(pos, np.ndarray) else pos.clone()
+    for comp, n in ((0, int(M)), (1, int(P))):
+        x = out[..., comp, :]
+        out[..., comp, :] = x - floor(x / n) * n
+    return out * dx
+
+
 PROFILE_LINES = ("energy_1", "energy_2", "enstrophy_1", "enstrophy_2", "interface", "psi_mean_1", "psi_mean_2",
                  "zeta_mean_1", "zeta_mean_2", "vort_flux_1", "vort_flux_2", "heat_flux")
 """The rows of a profiles record (layers 1-based, as the reference counts them), each a function

@@ -41,7 +41,9 @@ added the 20 of qg_spectra.hip (profiles/spectra/).  The profiles per latitude
 (qg_mi355_profiles.h) left all 210 functions of the seventeen earlier files identical and added
 the 12 of qg_profiles.hip (profiles/meridional/).  The 2-D and isotropic spectra
 (qg_mi355_spectra2d.h) left all 222 functions of the eighteen earlier files identical and added
-the 28 of qg_spectra2d.hip (profiles/spectra2d/isa_diff.txt).
+the 28 of qg_spectra2d.hip (profiles/spectra2d/isa_diff.txt).  The Lagrangian floats
+(qg_mi355_floats.h) left all 257 functions of the twenty earlier files identical and added the 4 of
+qg_floats.hip (profiles/floats/isa_diff.txt).
 """
 import re
 import sys
