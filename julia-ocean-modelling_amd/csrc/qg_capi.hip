@@ -11,12 +11,9 @@
 #include <new>
 
 #include "qg_common.hpp"
-#include "qg_mi355_profiles.h"
-#include "qg_mi355_spectra.h"
-#include "qg_mi355_spectra2d.h"
+#include "qg_owner.hpp"
 #include "qg_pcg.hpp"
 #include "qg_spectral.hpp"
-#include "qg_tracer.hpp"
 
 namespace qg {
 static std::atomic<int> g_form[QG_FORM_COUNT];  // qg_set_form (zero-initialised: automatic)
@@ -35,26 +32,6 @@ int comm_set_peer_gather(void *comm, int on, int64_t count);
 int comm_gather_records(void *user, const double *send, double *recv, int64_t count, hipStream_t s);
 int comm_init_host(void **comm, int nranks, int rank, qg_allgather_fn ag, qg_sendrecv_fn sr, void *user);
 int comm_unique_id(char out[128]);
-int diag_record_len();
-size_t diag_scratch_doubles();
-int launch_diagnostics(const void *z0, const void *z1, const void *p0, const void *p1, int esize, int64_t M,
-                       int64_t P, double dx, double *scratch, double *rec, hipStream_t s);
-// qg_spectra.hip
-bool spectra_supports(int64_t M, int64_t P);
-size_t spectra_scratch_doubles(int64_t M, int64_t P, int nmembers);
-int launch_spectra_twiddles(double *scratch, int64_t M, hipStream_t s);
-int launch_spectra(const void *z, const void *p, int esize, size_t F, int64_t M, int64_t P, double dx, size_t stride,
-                   int nmembers, double *scratch, double *out, hipStream_t s);
-// qg_spectra2d.hip
-bool spectra2d_supports(int64_t M, int64_t P);
-size_t spectra2d_scratch_doubles(int64_t M, int64_t P, int nmembers);
-int launch_spectra2d_twiddles(double *scratch, int64_t M, int64_t P, hipStream_t s);
-int launch_spectra2d(const void *z, const void *p, int esize, size_t F, int64_t M, int64_t P, double dx,
-                     size_t stride, int nmembers, double *scratch, double *out2d, double *iso, hipStream_t s);
-// qg_profiles.hip
-bool profiles_supports(int64_t M, int64_t P);
-int launch_profiles(const void *z, const void *p, int esize, size_t F, int64_t M, int64_t P, double dx, size_t stride,
-                    int nmembers, double *out, hipStream_t s);
 }  // namespace qg
 
 using namespace qg;
@@ -132,8 +109,7 @@ struct qg_ctx {
     double *wind = nullptr;  // [P] wind forcing of the local rows (qg_params.wind_tau0 != 0)
     double *diag = nullptr;  // diagnostics scratch: partial records | record | gathered records
     size_t diag_cap = 0;
-    double *spectra = nullptr;  // qg_spectra's scratch: twiddles | partial records (on first use)
-    double *spectra2d = nullptr;  // qg_spectra2d's: twiddles | half-spectra | 2-D record (on first use)
+    OwnerScratch scratch;    // the record families' (qg_owner.hpp)
     std::unique_ptr<SpectralSolver> spec;
     std::unique_ptr<PcgSolver> pcg;
     int last_status = QG_OK;  // of the last solve (PCG: QG_ERR_NOT_CONVERGED is kept here)
@@ -150,23 +126,27 @@ struct qg_ctx {
     int64_t row_words() const { return (int64_t)((p.M + 2) * esize / 8); }  // a row, in 8-byte words
 };
 
-// the owner's side of the tracer handles (qg_tracer.hpp): host only
-void qg::tracer_owner(const qg_ctx *c, TracerOwner *o) {
-    *o = TracerOwner{};
-    o->M = c->p.M;
-    o->P = c->p.P;
-    o->dx = c->p.dx;
-    o->dt = c->p.dt;
-    o->U = c->p.U;
-    o->device = c->device;
-    o->stream = c->stream;
-    o->F = c->F;
-    o->bound = c->initialised && c->zeta;
-    o->supported = c->esize == sizeof(double) && !c->distributed && c->nranks == 1 && c->p.M >= 3 && c->p.P >= 3;
-    if (o->bound && o->supported)
+// the owner's side of the record families (qg_owner.hpp): host only
+void qg::view(qg_ctx *c, StateView *v) {
+    *v = StateView{};
+    v->M = c->p.M;
+    v->P = c->p.P;
+    v->dx = c->p.dx;
+    v->dt = c->p.dt;
+    v->U = c->p.U;
+    v->device = c->device;
+    v->stream = c->stream;
+    v->esize = (int)c->esize;
+    v->F = c->F;
+    v->bound = c->initialised && c->zeta;
+    v->one_rank = !c->distributed && c->nranks == 1;
+    v->f64 = c->esize == sizeof(double);
+    v->uniform = true;
+    v->scratch = &c->scratch;
+    if (v->bound)  // (deferred lean keep-order: heads[0] names slot 2 while the new zeta waits there)
         for (int l = 0; l < 2; ++l) {
-            o->psi[l] = c->field(c->psi, l, c->heads[1]);
-            o->zeta[l] = c->field(c->zeta, l, c->heads[0]);
+            v->zeta[l] = c->fieldv(c->zeta, l, c->heads[0]);
+            v->psi[l] = c->fieldv(c->psi, l, c->heads[1]);
         }
 }
 
@@ -332,8 +312,7 @@ int qg_destroy(qg_ctx *c) {
     if (c->ov_ready) (void)hipEventDestroy(c->ov_ready);
     if (c->ov_halo) (void)hipEventDestroy(c->ov_halo);
     if (c->diag) (void)hipFree(c->diag);
-    if (c->spectra) (void)hipFree(c->spectra);
-    if (c->spectra2d) (void)hipFree(c->spectra2d);
+    c->scratch.release();
     if (c->wind) (void)hipFree(c->wind);
     drop_graphs(c);
     if (c->gstream) (void)hipStreamDestroy(c->gstream);
@@ -616,6 +595,14 @@ int qg_evolve_zeta(qg_ctx *c, int64_t timestep) {
     return c->esize == sizeof(float) ? evolve_zeta_t<float>(c, timestep) : evolve_zeta_t<double>(c, timestep);
 }
 
+// PCG: settle the pending certificate, then lt (host) <- the 8 doubles of the latch, waited for
+static int read_latch(qg_ctx *c, const char *what, double lt[8]) {
+    QG_HIP(hipSetDevice(c->device));
+    QG_CHECK(settle_pcg(c));
+    QG_HIP(hipMemcpyAsync(lt, c->pcg->latch(), sizeof(double) * 8, hipMemcpyDeviceToHost, c->stream));
+    return ctx_wait(c, what);
+}
+
 // Deferred PCG: report new certification failures the device has latched.  Polling (wait =
 // false, `steps` more steps enqueued on stream `on`): every QG_PACE_STEPS steps, read the copy
 // of the latch made one interval earlier -- waiting for it if it has not landed (bounded), so
@@ -641,12 +628,9 @@ static int poll_pcg(qg_ctx *c, bool wait, int steps = 1, hipStream_t on = nullpt
         return QG_OK;
     };
     if (wait) {
-        QG_CHECK(settle_pcg(c));
-        if (c->latch_armed) QG_CHECK(comm_wait(c->distributed ? c->comm : nullptr, c->stream, c->latch_ev,
-                                               "qg_run (PCG latch)"));
-        QG_HIP(hipMemcpyAsync(c->latch_host, c->pcg->latch(), sizeof(double) * 8, hipMemcpyDeviceToHost, c->stream));
-        QG_HIP(hipEventRecord(c->latch_ev, c->stream));
-        QG_CHECK(comm_wait(c->distributed ? c->comm : nullptr, c->stream, c->latch_ev, "qg_run (PCG latch)"));
+        // (an armed copy was enqueued before this one, on this stream or on the graph stream this
+        // stream has waited for: it has landed once this one has)
+        QG_CHECK(read_latch(c, "qg_run (PCG latch)", c->latch_host));
         c->latch_armed = false;
         return report();
     }
@@ -857,10 +841,7 @@ int qg_get_stats(qg_ctx *c, qg_stats *out) {
         out->relres[1] = c->pcg->relres(1);
         if (c->pcg->deferred()) {  // the last certified solve's residuals, from the latch
             double lt[8];
-            QG_HIP(hipSetDevice(c->device));
-            QG_CHECK(c->pcg->certify_pending(c->stream, c->distributed ? comm_allgather : nullptr, c->comm));
-            QG_HIP(hipMemcpyAsync(lt, c->pcg->latch(), sizeof(lt), hipMemcpyDeviceToHost, c->stream));
-            QG_CHECK(ctx_wait(c, "qg_get_stats"));
+            QG_CHECK(read_latch(c, "qg_get_stats", lt));
             out->relres[0] = lt[4];
             out->relres[1] = lt[5];
         }
@@ -985,10 +966,8 @@ int qg_synchronize(qg_ctx *c) {
     QG_CHECK(flush_ghosts(c));
     QG_CHECK(settle_zcopy(c));
     if (c->pcg && c->pcg->deferred()) {  // deferred PCG: new certification failures?
-        QG_CHECK(c->pcg->certify_pending(c->stream, c->distributed ? comm_allgather : nullptr, c->comm));
         double lt[8];
-        QG_HIP(hipMemcpyAsync(lt, c->pcg->latch(), sizeof(lt), hipMemcpyDeviceToHost, c->stream));
-        QG_CHECK(ctx_wait(c, "qg_synchronize"));
+        QG_CHECK(read_latch(c, "qg_synchronize", lt));
         if ((int64_t)lt[1] > c->cert_reported) {
             c->cert_reported = (int64_t)lt[1];
             return QG_ERR_NOT_CONVERGED;
@@ -1003,7 +982,7 @@ int qg_set_pcg_sync(qg_ctx *c, int sync) {
     c->pcg_sync = sync != 0 ? 1 : 0;
     if (c->pcg) {
         QG_HIP(hipSetDevice(c->device));
-        QG_CHECK(c->pcg->certify_pending(c->stream, c->distributed ? comm_allgather : nullptr, c->comm));
+        QG_CHECK(settle_pcg(c));
         c->pcg->set_deferred(sync == 0);
     }
     return QG_OK;
@@ -1012,11 +991,8 @@ int qg_set_pcg_sync(qg_ctx *c, int sync) {
 int qg_pcg_certificate(qg_ctx *c, int64_t *solves, int64_t *failures, int64_t *first_failure, double *worst_relres) {
     if (!c) return QG_ERR_INVALID_ARG;
     if (!c->pcg) return QG_ERR_UNSUPPORTED;
-    QG_HIP(hipSetDevice(c->device));
-    QG_CHECK(c->pcg->certify_pending(c->stream, c->distributed ? comm_allgather : nullptr, c->comm));
     double lt[8];
-    QG_HIP(hipMemcpyAsync(lt, c->pcg->latch(), sizeof(lt), hipMemcpyDeviceToHost, c->stream));
-    QG_CHECK(ctx_wait(c, "qg_pcg_certificate"));
+    QG_CHECK(read_latch(c, "qg_pcg_certificate", lt));
     if (solves) *solves = (int64_t)lt[0];
     if (failures) *failures = (int64_t)lt[1];
     if (first_failure) *first_failure = (int64_t)lt[2];
@@ -1241,135 +1217,6 @@ int qg_arakawa_J(const double *zeta, const double *psi, double *out, int64_t M, 
 int qg_fill_ghosts(double *b, int64_t M, int64_t P, void *stream) {
     if (!b || M < 1 || P < 1) return QG_ERR_INVALID_ARG;
     return launch_fill_ghosts(b, M, P, static_cast<hipStream_t>(stream));
-}
-
-// ---- zonal wavenumber spectra (include/qg_mi355_spectra.h; kernels in qg_spectra.hip) ------
-// the refusals that need the handle, in the header's order; then the scratch (on first use)
-static int spectra_ready(qg_ctx *c) {
-    if (!c->initialised || !c->zeta) return QG_ERR_NOT_BOUND;
-    if (c->distributed || c->nranks != 1 || !spectra_supports(c->p.M, c->p.P)) return QG_ERR_UNSUPPORTED;
-    if (c->spectra) return QG_OK;
-    QG_HIP(hipSetDevice(c->device));
-    if (hipMalloc((void **)&c->spectra, sizeof(double) * spectra_scratch_doubles(c->p.M, c->p.P, 1)) != hipSuccess) {
-        c->spectra = nullptr;
-        (void)hipGetLastError();
-        return QG_ERR_ALLOC;
-    }
-    return launch_spectra_twiddles(c->spectra, c->p.M, c->stream);
-}
-
-// the record of the newest state -> out (device); interior points only: no ghost flush
-static int spectra_record(qg_ctx *c, double *out) {
-    return launch_spectra(c->fieldv(c->zeta, 0, c->heads[0]), c->fieldv(c->psi, 0, c->heads[1]), (int)c->esize, c->F,
-                          c->p.M, c->p.P, c->p.dx, 0, 1, c->spectra, out, c->stream);
-}
-
-static bool aligned8(const void *p) { return reinterpret_cast<uintptr_t>(p) % sizeof(double) == 0; }
-
-int qg_spectra(qg_ctx *c, double *out) {
-    if (!c || !out || !aligned8(out)) return QG_ERR_INVALID_ARG;
-    QG_CHECK(spectra_ready(c));
-    QG_HIP(hipSetDevice(c->device));
-    return spectra_record(c, out);
-}
-
-int qg_run_spectra(qg_ctx *c, int64_t first_step, int64_t nsteps, int64_t every, double *records, int64_t capacity,
-                   int64_t *nrecords) {
-    if (!c || first_step < 1 || nsteps < 0 || every < 1 || !records || !aligned8(records)) return QG_ERR_INVALID_ARG;
-    const int64_t n = nsteps / every;
-    if (capacity < n) return QG_ERR_INVALID_ARG;
-    QG_CHECK(spectra_ready(c));
-    if (nrecords) *nrecords = n;
-    const size_t len = (size_t)QG_SPEC_LINES * (size_t)(c->p.M / 2 + 1);
-    int64_t k = 0;
-    for (int64_t t = first_step; t < first_step + nsteps; ++t) {
-        QG_CHECK(qg_step(c, t));
-        if ((t - first_step + 1) % every == 0) QG_CHECK(spectra_record(c, records + len * (size_t)k++));
-    }
-    return poll_pcg(c, true);  // as qg_run: a failed deferred certificate is reported by the run
-}
-
-// ---- zonal-mean profiles per latitude (include/qg_mi355_profiles.h; kernel in qg_profiles.hip) ----
-// the refusals that need the handle, in the header's order (no scratch: a row is complete in its
-// workgroup)
-static int profiles_ready(qg_ctx *c) {
-    if (!c->initialised || !c->zeta) return QG_ERR_NOT_BOUND;
-    if (c->distributed || c->nranks != 1 || !profiles_supports(c->p.M, c->p.P)) return QG_ERR_UNSUPPORTED;
-    return QG_OK;
-}
-
-// the record of the newest state -> out (device); interior points only: no ghost flush
-static int profiles_record(qg_ctx *c, double *out) {
-    return launch_profiles(c->fieldv(c->zeta, 0, c->heads[0]), c->fieldv(c->psi, 0, c->heads[1]), (int)c->esize, c->F,
-                           c->p.M, c->p.P, c->p.dx, 0, 1, out, c->stream);
-}
-
-int qg_profiles(qg_ctx *c, double *out) {
-    if (!c || !out || !aligned8(out)) return QG_ERR_INVALID_ARG;
-    QG_CHECK(profiles_ready(c));
-    QG_HIP(hipSetDevice(c->device));
-    return profiles_record(c, out);
-}
-
-int qg_run_profiles(qg_ctx *c, int64_t first_step, int64_t nsteps, int64_t every, double *records, int64_t capacity,
-                    int64_t *nrecords) {
-    if (!c || first_step < 1 || nsteps < 0 || every < 1 || !records || !aligned8(records)) return QG_ERR_INVALID_ARG;
-    const int64_t n = nsteps / every;
-    if (capacity < n) return QG_ERR_INVALID_ARG;
-    QG_CHECK(profiles_ready(c));
-    if (nrecords) *nrecords = n;
-    const size_t len = (size_t)QG_PROF_LINES * (size_t)c->p.P;
-    int64_t k = 0;
-    for (int64_t t = first_step; t < first_step + nsteps; ++t) {
-        QG_CHECK(qg_step(c, t));
-        if ((t - first_step + 1) % every == 0) QG_CHECK(profiles_record(c, records + len * (size_t)k++));
-    }
-    return poll_pcg(c, true);  // as qg_run: a failed deferred certificate is reported by the run
-}
-
-// ---- (kx, ky) and isotropic spectra (include/qg_mi355_spectra2d.h; kernels in qg_spectra2d.hip) ----
-// the refusals that need the handle, in the header's order; then the scratch (on first use)
-static int spectra2d_ready(qg_ctx *c) {
-    if (!c->initialised || !c->zeta) return QG_ERR_NOT_BOUND;
-    if (c->distributed || c->nranks != 1 || !spectra2d_supports(c->p.M, c->p.P)) return QG_ERR_UNSUPPORTED;
-    if (c->spectra2d) return QG_OK;
-    QG_HIP(hipSetDevice(c->device));
-    if (hipMalloc((void **)&c->spectra2d, sizeof(double) * spectra2d_scratch_doubles(c->p.M, c->p.P, 1)) !=
-        hipSuccess) {
-        c->spectra2d = nullptr;
-        (void)hipGetLastError();
-        return QG_ERR_ALLOC;
-    }
-    return launch_spectra2d_twiddles(c->spectra2d, c->p.M, c->p.P, c->stream);
-}
-
-// the records of the newest state (device; either may be null); interior points only
-static int spectra2d_record(qg_ctx *c, double *out2d, double *iso) {
-    return launch_spectra2d(c->fieldv(c->zeta, 0, c->heads[0]), c->fieldv(c->psi, 0, c->heads[1]), (int)c->esize,
-                            c->F, c->p.M, c->p.P, c->p.dx, 0, 1, c->spectra2d, out2d, iso, c->stream);
-}
-
-int qg_spectra2d(qg_ctx *c, double *out2d, double *iso) {
-    if (!c || (!out2d && !iso) || !aligned8(out2d) || !aligned8(iso)) return QG_ERR_INVALID_ARG;
-    QG_CHECK(spectra2d_ready(c));
-    QG_HIP(hipSetDevice(c->device));
-    return spectra2d_record(c, out2d, iso);
-}
-
-int qg_run_iso_spectra(qg_ctx *c, int64_t first_step, int64_t nsteps, int64_t every, double *records,
-                       int64_t capacity, int64_t *nrecords) {
-    if (!c || first_step < 1 || nsteps < 0 || every < 1 || !records || !aligned8(records)) return QG_ERR_INVALID_ARG;
-    const int64_t n = nsteps / every;
-    if (capacity < n) return QG_ERR_INVALID_ARG;
-    QG_CHECK(spectra2d_ready(c));
-    if (nrecords) *nrecords = n;
-    const size_t len = (size_t)QG_SPEC_LINES * (size_t)qg_iso_shells(c->p.M, c->p.P);
-    int64_t k = 0;
-    for (int64_t t = first_step; t < first_step + nsteps; ++t) {
-        QG_CHECK(qg_step(c, t));
-        if ((t - first_step + 1) % every == 0) QG_CHECK(spectra2d_record(c, nullptr, records + len * (size_t)k++));
-    }
-    return poll_pcg(c, true);  // as qg_run: a failed deferred certificate is reported by the run
 }
 
 }  // extern "C"

@@ -280,4 +280,11 @@ int launch_initialise_global(void *zeta, void *psi, void *f_store, int esize, in
                              int64_t P_total, int64_t j_offset, double amp, double S1, double S2,
                              double dx, uint64_t seed1, uint64_t seed2, hipStream_t s);
 
+// ---- monitoring diagnostics (qg_diag.hip; called for a context and, member by member, an ensemble) ----
+int diag_record_len();
+size_t diag_scratch_doubles();
+// rec (device, diag_record_len() doubles) <- the rank-local record; scratch from diag_scratch_doubles()
+int launch_diagnostics(const void *z0, const void *z1, const void *p0, const void *p1, int esize, int64_t M,
+                       int64_t P, double dx, double *scratch, double *rec, hipStream_t s);
+
 }  // namespace qg

@@ -15,7 +15,9 @@
 //   ens_spread_final     one workgroup folds the partials in a fixed order, applies 1/(M P) and
 //                        1/2 and stores the 16 doubles of the record
 // The geometry of the two spread launches is a function of (M, P) only.
-#include "qg_common.hpp"
+#include "qg_mi355_stats.h"
+
+#include "qg_owner.hpp"
 
 namespace qg {
 
@@ -204,13 +206,13 @@ SpreadGeom spread_geom(int64_t M, int64_t P) {
 }  // namespace
 
 // doubles of the spread's scratch: the partials, then one record
-size_t ens_stats_scratch_doubles(int64_t M, int64_t P) { return (size_t)NQL * spread_geom(M, P).nb() * NPART + NREC; }
+static size_t ens_stats_scratch_doubles(int64_t M, int64_t P) { return (size_t)NQL * spread_geom(M, P).nb() * NPART + NREC; }
 // where, in that scratch, qg_ens_spread's record lies
-size_t ens_stats_record_offset(int64_t M, int64_t P) { return (size_t)NQL * spread_geom(M, P).nb() * NPART; }
+static size_t ens_stats_record_offset(int64_t M, int64_t P) { return (size_t)NQL * spread_geom(M, P).nb() * NPART; }
 
 // mean, var (device, n doubles; var may be null) <- the moments over nmembers values per point,
 // x + i + b * stride
-int launch_ens_moments(const double *x, size_t n, size_t stride, int nmembers, double *mean, double *var,
+static int launch_ens_moments(const double *x, size_t n, size_t stride, int nmembers, double *mean, double *var,
                        hipStream_t s) {
     const size_t nblk = (n + MOM_T - 1) / MOM_T;
     ens_moments_kernel<<<dim3((unsigned)nblk), MOM_T, 0, s>>>(x, n, stride, nmembers, mean, var);
@@ -220,7 +222,7 @@ int launch_ens_moments(const double *x, size_t n, size_t stride, int nmembers, d
 
 // rec (device, 16 doubles) <- the spread record of the slots z (zeta) and p (psi) of member 0
 // (layer 0; F doubles per field); scratch from ens_stats_scratch_doubles()
-int launch_ens_spread(const double *z, const double *p, size_t F, int64_t M, int64_t P, size_t stride, int nmembers,
+static int launch_ens_spread(const double *z, const double *p, size_t F, int64_t M, int64_t P, size_t stride, int nmembers,
                       double step, double *scratch, double *rec, hipStream_t s) {
     const SpreadGeom g = spread_geom(M, P);
     const dim3 grid((unsigned)g.chunks, (unsigned)g.strips, NQL);
@@ -233,3 +235,59 @@ int launch_ens_spread(const double *z, const double *p, size_t F, int64_t M, int
 }
 
 }  // namespace qg
+
+// ---- the C-ABI (include/qg_mi355_stats.h): any bound ensemble (host code: pointer arithmetic only) ----
+using namespace qg;
+
+// the spread record of the newest state -> rec (device)
+static int spread_record(qg_ens *e, double step, double *rec) {
+    StateView v;
+    view(e, &v);
+    return launch_ens_spread(static_cast<const double *>(v.zeta[0]), static_cast<const double *>(v.psi[0]), v.F, v.M,
+                             v.P, v.member_stride, v.nmembers, step, v.scratch->stats, rec, v.stream);
+}
+
+extern "C" {
+
+int qg_ens_moments(qg_ens *e, int which, double *mean, double *var) {
+    if (!e || !mean || which < 0 || which > 1 || !aligned(mean, 8) || !aligned(var, 8)) return QG_ERR_INVALID_ARG;
+    StateView v;
+    view(e, &v);
+    if (!v.bound) return QG_ERR_NOT_BOUND;
+    QG_HIP(hipSetDevice(v.device));
+    // one slot is both layers: 2 F points
+    return launch_ens_moments(static_cast<const double *>(which ? v.psi[0] : v.zeta[0]), 2 * v.F, v.member_stride,
+                              v.nmembers, mean, var, v.stream);
+}
+
+int qg_ens_spread(qg_ens *e, qg_spread *out) {
+    if (!e || !out) return QG_ERR_INVALID_ARG;
+    StateView v;
+    view(e, &v);
+    if (!v.bound) return QG_ERR_NOT_BOUND;
+    static_assert(sizeof(qg_spread) == 16 * sizeof(double), "the record the kernels write");
+    QG_CHECK(ensure_scratch(&v.scratch->stats, ens_stats_scratch_doubles(v.M, v.P), v.device));
+    QG_HIP(hipSetDevice(v.device));
+    double *rec = v.scratch->stats + ens_stats_record_offset(v.M, v.P);
+    QG_CHECK(spread_record(e, 0.0, rec));
+    QG_HIP(hipMemcpyAsync(out, rec, sizeof(qg_spread), hipMemcpyDeviceToHost, v.stream));
+    QG_HIP(hipStreamSynchronize(v.stream));
+    return QG_OK;
+}
+
+int qg_ens_run_recorded(qg_ens *e, int64_t first_step, int64_t nsteps, int64_t every, qg_spread *records,
+                        int64_t capacity, int64_t *nrecords) {
+    if (!e) return QG_ERR_INVALID_ARG;
+    int64_t n;
+    QG_CHECK(check_recorded(first_step, nsteps, every, records, capacity, &n));
+    StateView v;
+    view(e, &v);
+    if (!v.bound) return QG_ERR_NOT_BOUND;
+    if (n > 0) QG_CHECK(ensure_scratch(&v.scratch->stats, ens_stats_scratch_doubles(v.M, v.P), v.device));
+    if (nrecords) *nrecords = n;
+    return run_recorded(first_step, nsteps, every, [&](int64_t t) { return qg_ens_step(e, t); }, [&](int64_t t, int64_t k) {
+        return spread_record(e, (double)t, reinterpret_cast<double *>(records + k));
+    });
+}
+
+}  // extern "C"

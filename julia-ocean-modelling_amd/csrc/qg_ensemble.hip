@@ -17,8 +17,8 @@
 //   R_d differs                             launch_tendency_sweep + solve_members on per-member
 //                                           tables (SpectralSolver::init_member_tables)
 //
-// Statistics across the members (include/qg_mi355_stats.h): the three entry points are at the end
-// of this file, their kernels in qg_ens_stats.hip.
+// The records of an ensemble (statistics across the members, spectra, profiles, tracers, floats)
+// live beside their kernels; this file gives them a view of the newest state (qg_owner.hpp).
 #include <cmath>
 #include <cstring>
 #include <memory>
@@ -27,43 +27,9 @@
 
 #include "qg_common.hpp"
 #include "qg_mi355_ensemble.h"
-#include "qg_mi355_profiles.h"
-#include "qg_mi355_spectra.h"
-#include "qg_mi355_spectra2d.h"
-#include "qg_mi355_stats.h"
 #include "qg_mi355_sweep.h"
+#include "qg_owner.hpp"
 #include "qg_spectral.hpp"
-#include "qg_tracer.hpp"
-
-namespace qg {
-int diag_record_len();
-size_t diag_scratch_doubles();
-int launch_diagnostics(const void *z0, const void *z1, const void *p0, const void *p1, int esize, int64_t M,
-                       int64_t P, double dx, double *scratch, double *rec, hipStream_t s);
-// qg_ens_stats.hip
-size_t ens_stats_scratch_doubles(int64_t M, int64_t P);
-size_t ens_stats_record_offset(int64_t M, int64_t P);
-int launch_ens_moments(const double *x, size_t n, size_t stride, int nmembers, double *mean, double *var,
-                       hipStream_t s);
-int launch_ens_spread(const double *z, const double *p, size_t F, int64_t M, int64_t P, size_t stride, int nmembers,
-                      double step, double *scratch, double *rec, hipStream_t s);
-// qg_spectra.hip
-bool spectra_supports(int64_t M, int64_t P);
-size_t spectra_scratch_doubles(int64_t M, int64_t P, int nmembers);
-int launch_spectra_twiddles(double *scratch, int64_t M, hipStream_t s);
-int launch_spectra(const void *z, const void *p, int esize, size_t F, int64_t M, int64_t P, double dx, size_t stride,
-                   int nmembers, double *scratch, double *out, hipStream_t s);
-// qg_spectra2d.hip
-bool spectra2d_supports(int64_t M, int64_t P);
-size_t spectra2d_scratch_doubles(int64_t M, int64_t P, int nmembers);
-int launch_spectra2d_twiddles(double *scratch, int64_t M, int64_t P, hipStream_t s);
-int launch_spectra2d(const void *z, const void *p, int esize, size_t F, int64_t M, int64_t P, double dx,
-                     size_t stride, int nmembers, double *scratch, double *out2d, double *iso, hipStream_t s);
-// qg_profiles.hip
-bool profiles_supports(int64_t M, int64_t P);
-int launch_profiles(const void *z, const void *p, int esize, size_t F, int64_t M, int64_t P, double dx, size_t stride,
-                    int nmembers, double *out, hipStream_t s);
-}  // namespace qg
 
 using namespace qg;
 
@@ -82,9 +48,7 @@ struct qg_ens {
     TendMember *rec = nullptr;         // device [nmembers] records: the sweep tendency (else null)
     bool sweep = false;                // made by qg_ens_create_sweep (the tracer handles refuse it)
     double *diag = nullptr;    // diagnostics: partial records (reused member after member) | nmembers records
-    double *stats = nullptr;   // cross-member statistics: partial sums | one record (on first use)
-    double *spectra = nullptr; // zonal spectra: twiddles | every member's partial records (on first use)
-    double *spectra2d = nullptr; // 2-D spectra: twiddles | one batch's half-spectra and 2-D records (on first use)
+    OwnerScratch scratch;      // the record families' (qg_owner.hpp)
     SpectralSolver spec;
     size_t F = 0;  // doubles per (M+2, P+2) field
 
@@ -92,25 +56,27 @@ struct qg_ens {
     double *field(double *base, int layer, int slot) const { return base + F * (size_t)(layer + 2 * slot); }
 };
 
-// the owner's side of the tracer handles (qg_tracer.hpp): host only
-void qg::tracer_owner(const qg_ens *e, TracerOwner *o) {
-    *o = TracerOwner{};
-    o->M = e->p.M;
-    o->P = e->p.P;
-    o->dx = e->p.dx;
-    o->dt = e->p.dt;
-    o->U = e->mp[0].U;
-    o->device = e->device;
-    o->stream = e->stream;
-    o->nmembers = e->nmembers;
-    o->F = e->F;
-    o->member_stride = e->member_stride();
-    o->bound = e->zeta != nullptr;
-    o->supported = !e->sweep && e->p.M >= 3 && e->p.P >= 3;  // (per-member U is left for later)
-    if (o->bound && o->supported)
+// the owner's side of the record families (qg_owner.hpp): host only
+void qg::view(qg_ens *e, StateView *v) {
+    *v = StateView{};
+    v->M = e->p.M;
+    v->P = e->p.P;
+    v->dx = e->p.dx;
+    v->dt = e->p.dt;
+    v->U = e->mp[0].U;
+    v->device = e->device;
+    v->stream = e->stream;
+    v->nmembers = e->nmembers;
+    v->F = e->F;
+    v->member_stride = e->member_stride();
+    v->bound = e->zeta != nullptr;
+    v->one_rank = v->f64 = true;
+    v->uniform = !e->sweep;  // (the tracers and floats: per-member U is left for later)
+    v->scratch = &e->scratch;
+    if (v->bound)
         for (int l = 0; l < 2; ++l) {
-            o->psi[l] = e->field(e->psi, l, e->heads[1]);
-            o->zeta[l] = e->field(e->zeta, l, e->heads[0]);
+            v->zeta[l] = e->field(e->zeta, l, e->heads[0]);
+            v->psi[l] = e->field(e->psi, l, e->heads[1]);
         }
 }
 
@@ -271,9 +237,7 @@ int qg_ens_destroy(qg_ens *e) {
     if (e->wind) (void)hipFree(e->wind);
     if (e->rec) (void)hipFree(e->rec);
     if (e->diag) (void)hipFree(e->diag);
-    if (e->stats) (void)hipFree(e->stats);
-    if (e->spectra) (void)hipFree(e->spectra);
-    if (e->spectra2d) (void)hipFree(e->spectra2d);
+    e->scratch.release();
     delete e;
     return QG_OK;
 }
@@ -425,195 +389,6 @@ int qg_ens_diagnostics(qg_ens *e, qg_diag *out) {
     QG_HIP(hipMemcpyAsync(out, recs, sizeof(qg_diag) * (size_t)e->nmembers, hipMemcpyDeviceToHost, e->stream));
     QG_HIP(hipStreamSynchronize(e->stream));
     for (int b = 0; b < e->nmembers; ++b) out[b].reserved = 0.0;
-    return QG_OK;
-}
-
-// ---- statistics across the members (include/qg_mi355_stats.h; kernels in qg_ens_stats.hip) ----
-static int ens_stats_scratch(qg_ens *e) {
-    if (e->stats) return QG_OK;
-    QG_HIP(hipSetDevice(e->device));
-    if (hipMalloc((void **)&e->stats, sizeof(double) * ens_stats_scratch_doubles(e->p.M, e->p.P)) != hipSuccess) {
-        e->stats = nullptr;
-        return QG_ERR_ALLOC;
-    }
-    return QG_OK;
-}
-
-// the spread record of the newest state -> rec (device)
-static int ens_spread_record(qg_ens *e, double step, double *rec) {
-    return launch_ens_spread(e->field(e->zeta, 0, e->heads[0]), e->field(e->psi, 0, e->heads[1]), e->F, e->p.M,
-                             e->p.P, e->member_stride(), e->nmembers, step, e->stats, rec, e->stream);
-}
-
-static bool aligned8(const void *p) { return reinterpret_cast<uintptr_t>(p) % sizeof(double) == 0; }
-
-int qg_ens_moments(qg_ens *e, int which, double *mean, double *var) {
-    if (!e || !mean || which < 0 || which > 1 || !aligned8(mean) || !aligned8(var)) return QG_ERR_INVALID_ARG;
-    if (!e->zeta) return QG_ERR_NOT_BOUND;
-    QG_HIP(hipSetDevice(e->device));
-    // one slot is both layers: 2 F points
-    return launch_ens_moments(e->field(which ? e->psi : e->zeta, 0, e->heads[which]), 2 * e->F, e->member_stride(),
-                              e->nmembers, mean, var, e->stream);
-}
-
-int qg_ens_spread(qg_ens *e, qg_spread *out) {
-    if (!e || !out) return QG_ERR_INVALID_ARG;
-    if (!e->zeta) return QG_ERR_NOT_BOUND;
-    static_assert(sizeof(qg_spread) == 16 * sizeof(double), "the record the kernels write");
-    QG_CHECK(ens_stats_scratch(e));
-    QG_HIP(hipSetDevice(e->device));
-    double *rec = e->stats + ens_stats_record_offset(e->p.M, e->p.P);
-    QG_CHECK(ens_spread_record(e, 0.0, rec));
-    QG_HIP(hipMemcpyAsync(out, rec, sizeof(qg_spread), hipMemcpyDeviceToHost, e->stream));
-    QG_HIP(hipStreamSynchronize(e->stream));
-    return QG_OK;
-}
-
-int qg_ens_run_recorded(qg_ens *e, int64_t first_step, int64_t nsteps, int64_t every, qg_spread *records,
-                        int64_t capacity, int64_t *nrecords) {
-    if (!e || first_step < 1 || nsteps < 0 || every < 1 || !records || !aligned8(records))
-        return QG_ERR_INVALID_ARG;
-    const int64_t n = nsteps / every;
-    if (capacity < n) return QG_ERR_INVALID_ARG;
-    if (!e->zeta) return QG_ERR_NOT_BOUND;
-    if (n > 0) QG_CHECK(ens_stats_scratch(e));
-    if (nrecords) *nrecords = n;
-    int64_t k = 0;
-    for (int64_t t = first_step; t < first_step + nsteps; ++t) {
-        QG_CHECK(qg_ens_step(e, t));
-        if ((t - first_step + 1) % every == 0)
-            QG_CHECK(ens_spread_record(e, (double)t, reinterpret_cast<double *>(records + k++)));
-    }
-    return QG_OK;
-}
-
-// ---- zonal wavenumber spectra (include/qg_mi355_spectra.h; kernels in qg_spectra.hip) ----
-// the refusals that need the handle, in the header's order; then the scratch (on first use)
-static int ens_spectra_ready(qg_ens *e) {
-    if (!e->zeta) return QG_ERR_NOT_BOUND;
-    if (!spectra_supports(e->p.M, e->p.P)) return QG_ERR_UNSUPPORTED;
-    if (e->spectra) return QG_OK;
-    QG_HIP(hipSetDevice(e->device));
-    if (hipMalloc((void **)&e->spectra, sizeof(double) * spectra_scratch_doubles(e->p.M, e->p.P, e->nmembers)) !=
-        hipSuccess) {
-        e->spectra = nullptr;
-        (void)hipGetLastError();
-        return QG_ERR_ALLOC;
-    }
-    return launch_spectra_twiddles(e->spectra, e->p.M, e->stream);
-}
-
-// every member's record of the newest state -> out (device): a single context's launches with
-// the member as the grid's second dimension
-static int ens_spectra_record(qg_ens *e, double *out) {
-    return launch_spectra(e->field(e->zeta, 0, e->heads[0]), e->field(e->psi, 0, e->heads[1]), (int)sizeof(double),
-                          e->F, e->p.M, e->p.P, e->p.dx, e->member_stride(), e->nmembers, e->spectra, out, e->stream);
-}
-
-int qg_ens_spectra(qg_ens *e, double *out) {
-    if (!e || !out || !aligned8(out)) return QG_ERR_INVALID_ARG;
-    QG_CHECK(ens_spectra_ready(e));
-    QG_HIP(hipSetDevice(e->device));
-    return ens_spectra_record(e, out);
-}
-
-int qg_ens_run_spectra(qg_ens *e, int64_t first_step, int64_t nsteps, int64_t every, double *records,
-                       int64_t capacity, int64_t *nrecords) {
-    if (!e || first_step < 1 || nsteps < 0 || every < 1 || !records || !aligned8(records)) return QG_ERR_INVALID_ARG;
-    const int64_t n = nsteps / every;
-    if (capacity < n) return QG_ERR_INVALID_ARG;
-    QG_CHECK(ens_spectra_ready(e));
-    if (nrecords) *nrecords = n;
-    const size_t len = (size_t)e->nmembers * QG_SPEC_LINES * (size_t)(e->p.M / 2 + 1);
-    int64_t k = 0;
-    for (int64_t t = first_step; t < first_step + nsteps; ++t) {
-        QG_CHECK(qg_ens_step(e, t));
-        if ((t - first_step + 1) % every == 0) QG_CHECK(ens_spectra_record(e, records + len * (size_t)k++));
-    }
-    return QG_OK;
-}
-
-// ---- zonal-mean profiles per latitude (include/qg_mi355_profiles.h; kernel in qg_profiles.hip) ----
-static int ens_profiles_ready(qg_ens *e) {
-    if (!e->zeta) return QG_ERR_NOT_BOUND;
-    if (!profiles_supports(e->p.M, e->p.P)) return QG_ERR_UNSUPPORTED;
-    return QG_OK;
-}
-
-// every member's record of the newest state -> out (device): a single context's launch with the
-// member as the grid's second dimension
-static int ens_profiles_record(qg_ens *e, double *out) {
-    return launch_profiles(e->field(e->zeta, 0, e->heads[0]), e->field(e->psi, 0, e->heads[1]), (int)sizeof(double),
-                           e->F, e->p.M, e->p.P, e->p.dx, e->member_stride(), e->nmembers, out, e->stream);
-}
-
-int qg_ens_profiles(qg_ens *e, double *out) {
-    if (!e || !out || !aligned8(out)) return QG_ERR_INVALID_ARG;
-    QG_CHECK(ens_profiles_ready(e));
-    QG_HIP(hipSetDevice(e->device));
-    return ens_profiles_record(e, out);
-}
-
-int qg_ens_run_profiles(qg_ens *e, int64_t first_step, int64_t nsteps, int64_t every, double *records,
-                        int64_t capacity, int64_t *nrecords) {
-    if (!e || first_step < 1 || nsteps < 0 || every < 1 || !records || !aligned8(records)) return QG_ERR_INVALID_ARG;
-    const int64_t n = nsteps / every;
-    if (capacity < n) return QG_ERR_INVALID_ARG;
-    QG_CHECK(ens_profiles_ready(e));
-    if (nrecords) *nrecords = n;
-    const size_t len = (size_t)e->nmembers * QG_PROF_LINES * (size_t)e->p.P;
-    int64_t k = 0;
-    for (int64_t t = first_step; t < first_step + nsteps; ++t) {
-        QG_CHECK(qg_ens_step(e, t));
-        if ((t - first_step + 1) % every == 0) QG_CHECK(ens_profiles_record(e, records + len * (size_t)k++));
-    }
-    return QG_OK;
-}
-
-// ---- (kx, ky) and isotropic spectra (include/qg_mi355_spectra2d.h; kernels in qg_spectra2d.hip) ----
-static int ens_spectra2d_ready(qg_ens *e) {
-    if (!e->zeta) return QG_ERR_NOT_BOUND;
-    if (!spectra2d_supports(e->p.M, e->p.P)) return QG_ERR_UNSUPPORTED;
-    if (e->spectra2d) return QG_OK;
-    QG_HIP(hipSetDevice(e->device));
-    if (hipMalloc((void **)&e->spectra2d,
-                  sizeof(double) * spectra2d_scratch_doubles(e->p.M, e->p.P, e->nmembers)) != hipSuccess) {
-        e->spectra2d = nullptr;
-        (void)hipGetLastError();
-        return QG_ERR_ALLOC;
-    }
-    return launch_spectra2d_twiddles(e->spectra2d, e->p.M, e->p.P, e->stream);
-}
-
-// every member's records of the newest state (device; either may be null): a single context's
-// launches with the member as the grid's second dimension, batch after batch
-static int ens_spectra2d_record(qg_ens *e, double *out2d, double *iso) {
-    return launch_spectra2d(e->field(e->zeta, 0, e->heads[0]), e->field(e->psi, 0, e->heads[1]), (int)sizeof(double),
-                            e->F, e->p.M, e->p.P, e->p.dx, e->member_stride(), e->nmembers, e->spectra2d, out2d, iso,
-                            e->stream);
-}
-
-int qg_ens_spectra2d(qg_ens *e, double *out2d, double *iso) {
-    if (!e || (!out2d && !iso) || !aligned8(out2d) || !aligned8(iso)) return QG_ERR_INVALID_ARG;
-    QG_CHECK(ens_spectra2d_ready(e));
-    QG_HIP(hipSetDevice(e->device));
-    return ens_spectra2d_record(e, out2d, iso);
-}
-
-int qg_ens_run_iso_spectra(qg_ens *e, int64_t first_step, int64_t nsteps, int64_t every, double *records,
-                           int64_t capacity, int64_t *nrecords) {
-    if (!e || first_step < 1 || nsteps < 0 || every < 1 || !records || !aligned8(records)) return QG_ERR_INVALID_ARG;
-    const int64_t n = nsteps / every;
-    if (capacity < n) return QG_ERR_INVALID_ARG;
-    QG_CHECK(ens_spectra2d_ready(e));
-    if (nrecords) *nrecords = n;
-    const size_t len = (size_t)e->nmembers * QG_SPEC_LINES * (size_t)qg_iso_shells(e->p.M, e->p.P);
-    int64_t k = 0;
-    for (int64_t t = first_step; t < first_step + nsteps; ++t) {
-        QG_CHECK(qg_ens_step(e, t));
-        if ((t - first_step + 1) % every == 0)
-            QG_CHECK(ens_spectra2d_record(e, nullptr, records + len * (size_t)k++));
-    }
     return QG_OK;
 }
 

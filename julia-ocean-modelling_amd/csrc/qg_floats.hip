@@ -19,7 +19,7 @@
 
 #include <new>
 
-#include "qg_tracer.hpp"
+#include "qg_owner.hpp"
 
 namespace qg {
 
@@ -223,8 +223,7 @@ int stat_strips(int64_t n0, int64_t n1) {
 using namespace qg;
 
 struct qg_floats {
-    qg_ctx *ctx = nullptr;  // the owner: one of the two
-    qg_ens *ens = nullptr;
+    Owner owner;
     int64_t n0 = 0, n1 = 0, N = 0;
     double *pos = nullptr, *origin = nullptr, *hist = nullptr;
     int head = 0;         // the slot of hist that holds the newer velocities
@@ -233,29 +232,25 @@ struct qg_floats {
     double *part = nullptr;  // the statistics' partial sums
     int device = 0;
 
-    void owner(TracerOwner *o) const {
-        if (ctx) tracer_owner(ctx, o);
-        else tracer_owner(ens, o);
-    }
     size_t slot_off(int slot) const { return (size_t)slot * 2 * (size_t)N; }
 };
 
-static bool aligned(const void *p, size_t n) { return reinterpret_cast<uintptr_t>(p) % n == 0; }
+// the header's rule: F64, one rank and no transport, no per-member physics, M and P >= 3
+static bool floats_supported(const StateView &o) { return o.one_rank && o.f64 && o.uniform && o.M >= 3 && o.P >= 3; }
 
-static int floats_create(qg_ctx *ctx, qg_ens *ens, int64_t n0, int64_t n1, qg_floats **out) {
+static int floats_create(Owner owner, int64_t n0, int64_t n1, qg_floats **out) {
     if (!out) return QG_ERR_INVALID_ARG;
     *out = nullptr;
-    if ((!ctx && !ens) || n0 < 0 || n1 < 0 || n0 > NMAX || n1 > NMAX || n0 + n1 < 1) return QG_ERR_INVALID_ARG;
+    if (!owner || n0 < 0 || n1 < 0 || n0 > NMAX || n1 > NMAX || n0 + n1 < 1) return QG_ERR_INVALID_ARG;
     qg_floats *t = new (std::nothrow) qg_floats();
     if (!t) return QG_ERR_ALLOC;
-    t->ctx = ctx;
-    t->ens = ens;
+    t->owner = owner;
     t->n0 = n0;
     t->n1 = n1;
     t->N = n0 + n1;
-    TracerOwner o;
-    t->owner(&o);
-    if (!o.supported) {
+    StateView o;
+    owner.view(&o);
+    if (!floats_supported(o)) {
         delete t;
         return QG_ERR_UNSUPPORTED;
     }
@@ -271,15 +266,15 @@ static int floats_create(qg_ctx *ctx, qg_ens *ens, int64_t n0, int64_t n1, qg_fl
 }
 
 // the refusals of a call that reads the arrays, in the header's order
-static int floats_ready(const qg_floats *t, TracerOwner *o) {
+static int floats_ready(const qg_floats *t, StateView *o) {
     if (!t->pos) return QG_ERR_NOT_BOUND;
-    t->owner(o);
-    if (!o->supported) return QG_ERR_UNSUPPORTED;  // (a transport attached since the create)
+    t->owner.view(o);
+    if (!floats_supported(*o)) return QG_ERR_UNSUPPORTED;  // (a transport attached since the create)
     if (!o->bound || !t->ready) return QG_ERR_NOT_BOUND;
     return QG_OK;
 }
 
-static FltArgs flt_args(const qg_floats *t, const TracerOwner &o, const double *const fld[2]) {
+static FltArgs flt_args(const qg_floats *t, const StateView &o, const void *const fld[2]) {
     FltArgs a{};
     a.M = (int)o.M;
     a.P = (int)o.P;
@@ -290,17 +285,17 @@ static FltArgs flt_args(const qg_floats *t, const TracerOwner &o, const double *
     a.dx = o.dx;
     a.dt = o.dt;
     a.U = o.U;
-    a.fld[0] = fld[0];
-    a.fld[1] = fld[1];
+    a.fld[0] = static_cast<const double *>(fld[0]);  // (F64: floats_supported)
+    a.fld[1] = static_cast<const double *>(fld[1]);
     a.pos = t->pos;
     return a;
 }
 
-static dim3 flt_grid(const qg_floats *t, const TracerOwner &o) {
+static dim3 flt_grid(const qg_floats *t, const StateView &o) {
     return dim3((unsigned)((t->N + ADV_T - 1) / ADV_T), (unsigned)o.nmembers);  // <= 2^19 x 65535
 }
 
-static int floats_advance(qg_floats *t, const TracerOwner &o) {
+static int floats_advance(qg_floats *t, const StateView &o) {
     FltArgs a = flt_args(t, o, o.psi);
     a.ab3 = t->age >= 2;
     a.g2 = t->hist + t->slot_off(t->head);
@@ -318,7 +313,7 @@ static int floats_advance(qg_floats *t, const TracerOwner &o) {
     return QG_OK;
 }
 
-static int floats_record(qg_floats *t, const TracerOwner &o, double *out) {
+static int floats_record(qg_floats *t, const StateView &o, double *out) {
     StatArgs a{};
     a.N = t->N;
     a.n0 = t->n0;
@@ -340,11 +335,11 @@ static int floats_record(qg_floats *t, const TracerOwner &o, double *out) {
 extern "C" {
 
 int qg_floats_create(qg_ctx *owner, int64_t n0, int64_t n1, qg_floats **out) {
-    return floats_create(owner, nullptr, n0, n1, out);
+    return floats_create(Owner{owner, nullptr}, n0, n1, out);
 }
 
 int qg_ens_floats_create(qg_ens *owner, int64_t n0, int64_t n1, qg_floats **out) {
-    return floats_create(nullptr, owner, n0, n1, out);
+    return floats_create(Owner{nullptr, owner}, n0, n1, out);
 }
 
 int qg_floats_destroy(qg_floats *t) {
@@ -370,9 +365,9 @@ int qg_floats_bind(qg_floats *t, double *pos, double *origin, double *hist) {
 int qg_floats_reset(qg_floats *t) {
     if (!t) return QG_ERR_INVALID_ARG;
     if (!t->pos) return QG_ERR_NOT_BOUND;
-    TracerOwner o;
-    t->owner(&o);
-    if (!o.supported) return QG_ERR_UNSUPPORTED;
+    StateView o;
+    t->owner.view(&o);
+    if (!floats_supported(o)) return QG_ERR_UNSUPPORTED;
     QG_HIP(hipSetDevice(o.device));
     const size_t n = (size_t)o.nmembers * 2 * (size_t)t->N;
     QG_HIP(hipMemcpyAsync(t->origin, t->pos, sizeof(double) * n, hipMemcpyDeviceToDevice, o.stream));
@@ -385,54 +380,45 @@ int qg_floats_reset(qg_floats *t) {
 
 int qg_floats_advance(qg_floats *t) {
     if (!t) return QG_ERR_INVALID_ARG;
-    TracerOwner o;
+    StateView o;
     QG_CHECK(floats_ready(t, &o));
     return floats_advance(t, o);
 }
 
 int qg_floats_step(qg_floats *t, int64_t timestep) {
     if (!t || timestep < 1) return QG_ERR_INVALID_ARG;
-    TracerOwner o;
+    StateView o;
     QG_CHECK(floats_ready(t, &o));
     QG_CHECK(floats_advance(t, o));
-    return t->ctx ? qg_step(t->ctx, timestep) : qg_ens_step(t->ens, timestep);
+    return t->owner.step(timestep);
 }
 
 int qg_floats_run(qg_floats *t, int64_t first_step, int64_t nsteps, int64_t every, double *traj, double *stats,
                   int64_t capacity, int64_t *nrecords) {
     if (!t || first_step < 1 || nsteps < 0) return QG_ERR_INVALID_ARG;
     const bool rec = traj || stats;
-    int64_t n = 0;
+    int64_t n = 0;  // (every and capacity count only with a record pointer)
     if (rec) {
-        if (every < 1 || !aligned(traj, 8) || !aligned(stats, 8)) return QG_ERR_INVALID_ARG;
-        n = nsteps / every;
-        if (capacity < n) return QG_ERR_INVALID_ARG;
+        if (!aligned(traj, 8) || !aligned(stats, 8)) return QG_ERR_INVALID_ARG;
+        QG_CHECK(check_recorded(first_step, nsteps, every, traj ? traj : stats, capacity, &n));
     }
-    TracerOwner o;
+    StateView o;
     QG_CHECK(floats_ready(t, &o));
     if (nrecords) *nrecords = n;
     const size_t tlen = (size_t)o.nmembers * 2 * (size_t)t->N, slen = (size_t)o.nmembers * 2 * QG_FLT_LINES;
-    int64_t k = 0;
-    for (int64_t s = first_step; s < first_step + nsteps; ++s) {
-        QG_CHECK(qg_floats_step(t, s));
-        if (rec && (s - first_step + 1) % every == 0) {
-            if (traj)
-                QG_HIP(hipMemcpyAsync(traj + tlen * (size_t)k, t->pos, sizeof(double) * tlen, hipMemcpyDeviceToDevice,
-                                      o.stream));
-            if (stats) {
-                t->owner(&o);
-                QG_CHECK(floats_record(t, o, stats + slen * (size_t)k));
-            }
-            ++k;
-        }
-    }
-    // as qg_run / qg_ens_run end (a context: a failed deferred PCG certificate is reported here)
-    return t->ctx ? qg_run(t->ctx, first_step + nsteps, 0) : qg_ens_run(t->ens, first_step + nsteps, 0);
+    QG_CHECK(run_recorded(first_step, nsteps, rec ? every : 0, [&](int64_t s) { return qg_floats_step(t, s); },
+                          [&](int64_t, int64_t k) -> int {
+                              if (traj)
+                                  QG_HIP(hipMemcpyAsync(traj + tlen * (size_t)k, t->pos, sizeof(double) * tlen,
+                                                        hipMemcpyDeviceToDevice, o.stream));
+                              return stats ? floats_record(t, o, stats + slen * (size_t)k) : QG_OK;
+                          }));
+    return t->owner.finish(first_step + nsteps);
 }
 
 int qg_floats_stats(qg_floats *t, double *out) {
     if (!t || !out || !aligned(out, 8)) return QG_ERR_INVALID_ARG;
-    TracerOwner o;
+    StateView o;
     QG_CHECK(floats_ready(t, &o));
     QG_HIP(hipSetDevice(o.device));
     return floats_record(t, o, out);
@@ -440,7 +426,7 @@ int qg_floats_stats(qg_floats *t, double *out) {
 
 int qg_floats_sample(qg_floats *t, int field, double *out) {
     if (!t || !out || !aligned(out, 8) || (field != QG_FLT_PSI && field != QG_FLT_ZETA)) return QG_ERR_INVALID_ARG;
-    TracerOwner o;
+    StateView o;
     QG_CHECK(floats_ready(t, &o));
     FltArgs a = flt_args(t, o, field == QG_FLT_PSI ? o.psi : o.zeta);
     a.out = out;

@@ -25,7 +25,7 @@
 // load).  HBM-bound at large sizes: 4 fields read once, plus one psi row per strip.
 #include "qg_mi355_profiles.h"
 
-#include "qg_common.hpp"
+#include "qg_owner.hpp"
 
 namespace qg {
 
@@ -240,11 +240,11 @@ int launch_width(const ProfArgs &a, int nmembers, hipStream_t s) {
 }  // namespace
 
 // (the kernel indexes rows and columns with int)
-bool profiles_supports(int64_t M, int64_t P) { return M >= 3 && P >= 3 && M < (1 << 30) && P < (1 << 30); }
+static bool profiles_supports(int64_t M, int64_t P) { return M >= 3 && P >= 3 && M < (1 << 30) && P < (1 << 30); }
 
 // out (device, [nmembers][LINES][P]) <- the records of the slots z (zeta) and p (psi) of member 0
 // (layer 0; F elements per field of esize bytes; members `stride` elements apart)
-int launch_profiles(const void *z, const void *p, int esize, size_t F, int64_t M, int64_t P, double dx, size_t stride,
+static int launch_profiles(const void *z, const void *p, int esize, size_t F, int64_t M, int64_t P, double dx, size_t stride,
                     int nmembers, double *out, hipStream_t s) {
     ProfArgs a{};
     a.z = z;
@@ -262,3 +262,63 @@ int launch_profiles(const void *z, const void *p, int esize, size_t F, int64_t M
 }
 
 }  // namespace qg
+
+// ---- the C-ABI (include/qg_mi355_profiles.h), once for both owners -------------------------------
+using namespace qg;
+
+// the refusals that need the handle, in the header's order (no scratch: a row is complete in its
+// workgroup)
+static int profiles_ready(Owner o, StateView *v) {
+    o.view(v);
+    if (!v->bound) return QG_ERR_NOT_BOUND;
+    if (!v->one_rank || !profiles_supports(v->M, v->P)) return QG_ERR_UNSUPPORTED;
+    return QG_OK;
+}
+
+// every member's record of the newest state -> out (device); interior points only: no ghost flush
+static int profiles_record(Owner o, double *out) {
+    StateView v;
+    o.view(&v);
+    return launch_profiles(v.zeta[0], v.psi[0], v.esize, v.F, v.M, v.P, v.dx, v.member_stride, v.nmembers, out,
+                           v.stream);
+}
+
+static int profiles_now(Owner o, double *out) {
+    if (!o || !out || !aligned(out, 8)) return QG_ERR_INVALID_ARG;
+    StateView v;
+    QG_CHECK(profiles_ready(o, &v));
+    QG_HIP(hipSetDevice(v.device));
+    return profiles_record(o, out);
+}
+
+static int profiles_run(Owner o, int64_t first_step, int64_t nsteps, int64_t every, double *records, int64_t capacity,
+                        int64_t *nrecords) {
+    if (!o) return QG_ERR_INVALID_ARG;
+    int64_t n;
+    QG_CHECK(check_recorded(first_step, nsteps, every, records, capacity, &n));
+    StateView v;
+    QG_CHECK(profiles_ready(o, &v));
+    if (nrecords) *nrecords = n;
+    const size_t len = (size_t)v.nmembers * QG_PROF_LINES * (size_t)v.P;
+    QG_CHECK(run_recorded(first_step, nsteps, every, [&](int64_t t) { return o.step(t); },
+                          [&](int64_t, int64_t k) { return profiles_record(o, records + len * (size_t)k); }));
+    return o.finish(first_step + nsteps);
+}
+
+extern "C" {
+
+int qg_profiles(qg_ctx *c, double *out) { return profiles_now(Owner{c, nullptr}, out); }
+
+int qg_ens_profiles(qg_ens *e, double *out) { return profiles_now(Owner{nullptr, e}, out); }
+
+int qg_run_profiles(qg_ctx *c, int64_t first_step, int64_t nsteps, int64_t every, double *records, int64_t capacity,
+                    int64_t *nrecords) {
+    return profiles_run(Owner{c, nullptr}, first_step, nsteps, every, records, capacity, nrecords);
+}
+
+int qg_ens_run_profiles(qg_ens *e, int64_t first_step, int64_t nsteps, int64_t every, double *records,
+                        int64_t capacity, int64_t *nrecords) {
+    return profiles_run(Owner{nullptr, e}, first_step, nsteps, every, records, capacity, nrecords);
+}
+
+}  // extern "C"

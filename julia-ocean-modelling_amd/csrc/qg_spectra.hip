@@ -17,6 +17,7 @@
 // The geometry is a function of (M, P) only, and a single context is the launch with one member.
 // Everything accumulates in F64, also for an F32 state (converted at the load).
 #include "qg_mi355_spectra.h"
+#include "qg_owner.hpp"
 #include "qg_spec_pow2.hpp"
 
 namespace qg {
@@ -222,10 +223,10 @@ int strips(int64_t P) { return (int)(P < MAX_STRIPS ? P : MAX_STRIPS); }
 
 }  // namespace
 
-bool spectra_supports(int64_t M, int64_t P) { return M >= 8 && M <= 2048 && (M & (M - 1)) == 0 && P >= 3; }
+static bool spectra_supports(int64_t M, int64_t P) { return M >= 8 && M <= 2048 && (M & (M - 1)) == 0 && P >= 3; }
 
 // doubles of a handle's scratch: the twiddles, then the partial records
-size_t spectra_scratch_doubles(int64_t M, int64_t P, int nmembers) {
+static size_t spectra_scratch_doubles(int64_t M, int64_t P, int nmembers) {
     return 2 * (size_t)M + (size_t)nmembers * strips(P) * LINES * (size_t)(M / 2 + 1);
 }
 
@@ -239,7 +240,7 @@ int launch_spectra_twiddles(double *scratch, int64_t M, hipStream_t s) {
 // out (device, [nmembers][LINES][M/2+1]) <- the records of the slots z (zeta) and p (psi) of
 // member 0 (layer 0; F elements per field of esize bytes; members `stride` elements apart);
 // scratch from spectra_scratch_doubles()
-int launch_spectra(const void *z, const void *p, int esize, size_t F, int64_t M, int64_t P, double dx, size_t stride,
+static int launch_spectra(const void *z, const void *p, int esize, size_t F, int64_t M, int64_t P, double dx, size_t stride,
                    int nmembers, double *scratch, double *out, hipStream_t s) {
     SpectraArgs a{};
     a.z = z;
@@ -266,3 +267,65 @@ int launch_spectra(const void *z, const void *p, int esize, size_t F, int64_t M,
 }
 
 }  // namespace qg
+
+// ---- the C-ABI (include/qg_mi355_spectra.h), once for both owners --------------------------------
+using namespace qg;
+
+// the refusals that need the handle, in the header's order; then the scratch (on first use)
+static int spectra_ready(Owner o, StateView *v) {
+    o.view(v);
+    if (!v->bound) return QG_ERR_NOT_BOUND;
+    if (!v->one_rank || !spectra_supports(v->M, v->P)) return QG_ERR_UNSUPPORTED;
+    double **slot = &v->scratch->spectra;
+    if (*slot) return QG_OK;
+    QG_CHECK(ensure_scratch(slot, spectra_scratch_doubles(v->M, v->P, v->nmembers), v->device));
+    return launch_spectra_twiddles(*slot, v->M, v->stream);
+}
+
+// every member's record of the newest state -> out (device); interior points only: no ghost flush
+static int spectra_record(Owner o, double *out) {
+    StateView v;
+    o.view(&v);
+    return launch_spectra(v.zeta[0], v.psi[0], v.esize, v.F, v.M, v.P, v.dx, v.member_stride, v.nmembers,
+                          v.scratch->spectra, out, v.stream);
+}
+
+static int spectra_now(Owner o, double *out) {
+    if (!o || !out || !aligned(out, 8)) return QG_ERR_INVALID_ARG;
+    StateView v;
+    QG_CHECK(spectra_ready(o, &v));
+    QG_HIP(hipSetDevice(v.device));
+    return spectra_record(o, out);
+}
+
+static int spectra_run(Owner o, int64_t first_step, int64_t nsteps, int64_t every, double *records, int64_t capacity,
+                       int64_t *nrecords) {
+    if (!o) return QG_ERR_INVALID_ARG;
+    int64_t n;
+    QG_CHECK(check_recorded(first_step, nsteps, every, records, capacity, &n));
+    StateView v;
+    QG_CHECK(spectra_ready(o, &v));
+    if (nrecords) *nrecords = n;
+    const size_t len = (size_t)v.nmembers * QG_SPEC_LINES * (size_t)(v.M / 2 + 1);
+    QG_CHECK(run_recorded(first_step, nsteps, every, [&](int64_t t) { return o.step(t); },
+                          [&](int64_t, int64_t k) { return spectra_record(o, records + len * (size_t)k); }));
+    return o.finish(first_step + nsteps);
+}
+
+extern "C" {
+
+int qg_spectra(qg_ctx *c, double *out) { return spectra_now(Owner{c, nullptr}, out); }
+
+int qg_ens_spectra(qg_ens *e, double *out) { return spectra_now(Owner{nullptr, e}, out); }
+
+int qg_run_spectra(qg_ctx *c, int64_t first_step, int64_t nsteps, int64_t every, double *records, int64_t capacity,
+                   int64_t *nrecords) {
+    return spectra_run(Owner{c, nullptr}, first_step, nsteps, every, records, capacity, nrecords);
+}
+
+int qg_ens_run_spectra(qg_ens *e, int64_t first_step, int64_t nsteps, int64_t every, double *records,
+                       int64_t capacity, int64_t *nrecords) {
+    return spectra_run(Owner{nullptr, e}, first_step, nsteps, every, records, capacity, nrecords);
+}
+
+}  // extern "C"

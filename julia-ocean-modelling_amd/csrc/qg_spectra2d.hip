@@ -35,12 +35,10 @@
 // Members are passed over in batches of spectra2d_batch() so that the scratch stays bounded;
 // every member's workgroups do the same work in any batch.
 #include "qg_mi355_spectra2d.h"
+#include "qg_owner.hpp"
 #include "qg_spec_pow2.hpp"
 
 namespace qg {
-
-// qg_spectra.hip
-int launch_spectra_twiddles(double *scratch, int64_t M, hipStream_t s);
 
 namespace {
 
@@ -370,10 +368,10 @@ size_t rec_doubles(int64_t M, int64_t P) { return (size_t)LINES * (size_t)P * (s
 
 }  // namespace
 
-bool spectra2d_supports(int64_t M, int64_t P) { return pow2_in_range(M) && pow2_in_range(P); }
+static bool spectra2d_supports(int64_t M, int64_t P) { return pow2_in_range(M) && pow2_in_range(P); }
 
 // members per launch: a function of (M, P) and the member count's cap only
-int spectra2d_batch(int64_t M, int64_t P, int nmembers) {
+static int spectra2d_batch(int64_t M, int64_t P, int nmembers) {
     size_t nb = BATCH_DOUBLES / (half_doubles(M, P) + rec_doubles(M, P));
     if (nb < 1) nb = 1;
     if (nb > (size_t)MAX_BATCH) nb = MAX_BATCH;
@@ -382,13 +380,13 @@ int spectra2d_batch(int64_t M, int64_t P, int nmembers) {
 
 // doubles of a handle's scratch: the twiddles of M and of P, then one batch's half-spectra and
 // 2-D records
-size_t spectra2d_scratch_doubles(int64_t M, int64_t P, int nmembers) {
+static size_t spectra2d_scratch_doubles(int64_t M, int64_t P, int nmembers) {
     return 2 * (size_t)M + 2 * (size_t)P +
            (size_t)spectra2d_batch(M, P, nmembers) * (half_doubles(M, P) + rec_doubles(M, P));
 }
 
 // fills the twiddles of a fresh scratch (once, before its first launch_spectra2d, in stream order)
-int launch_spectra2d_twiddles(double *scratch, int64_t M, int64_t P, hipStream_t s) {
+static int launch_spectra2d_twiddles(double *scratch, int64_t M, int64_t P, hipStream_t s) {
     QG_CHECK(launch_spectra_twiddles(scratch, M, s));
     return launch_spectra_twiddles(scratch + 2 * (size_t)M, P, s);
 }
@@ -396,7 +394,7 @@ int launch_spectra2d_twiddles(double *scratch, int64_t M, int64_t P, hipStream_t
 // out2d (device, [nmembers][LINES][P][M/2+1], or null) and iso (device, [nmembers][LINES][NK], or
 // null) <- the records of the slots z (zeta) and p (psi) of member 0 (layer 0; F elements per
 // field of esize bytes; members `stride` elements apart); scratch from spectra2d_scratch_doubles()
-int launch_spectra2d(const void *z, const void *p, int esize, size_t F, int64_t M, int64_t P, double dx,
+static int launch_spectra2d(const void *z, const void *p, int esize, size_t F, int64_t M, int64_t P, double dx,
                      size_t stride, int nmembers, double *scratch, double *out2d, double *iso, hipStream_t s) {
     const int nb = spectra2d_batch(M, P, nmembers);
     const int NK = qg_iso_shells(M, P);
@@ -445,8 +443,68 @@ int launch_spectra2d(const void *z, const void *p, int esize, size_t F, int64_t 
 
 }  // namespace qg
 
-// ---- the pure host functions of include/qg_mi355_spectra2d.h ------------------------------------
+// ---- the C-ABI (include/qg_mi355_spectra2d.h), once for both owners ------------------------------
+using namespace qg;
+
+// the refusals that need the handle, in the header's order; then the scratch (on first use)
+static int spectra2d_ready(Owner o, StateView *v) {
+    o.view(v);
+    if (!v->bound) return QG_ERR_NOT_BOUND;
+    if (!v->one_rank || !spectra2d_supports(v->M, v->P)) return QG_ERR_UNSUPPORTED;
+    double **slot = &v->scratch->spectra2d;
+    if (*slot) return QG_OK;
+    QG_CHECK(ensure_scratch(slot, spectra2d_scratch_doubles(v->M, v->P, v->nmembers), v->device));
+    return launch_spectra2d_twiddles(*slot, v->M, v->P, v->stream);
+}
+
+// every member's records of the newest state (device; either may be null); interior points only
+static int spectra2d_record(Owner o, double *out2d, double *iso) {
+    StateView v;
+    o.view(&v);
+    return launch_spectra2d(v.zeta[0], v.psi[0], v.esize, v.F, v.M, v.P, v.dx, v.member_stride, v.nmembers,
+                            v.scratch->spectra2d, out2d, iso, v.stream);
+}
+
+static int spectra2d_now(Owner o, double *out2d, double *iso) {
+    if (!o || (!out2d && !iso) || !aligned(out2d, 8) || !aligned(iso, 8)) return QG_ERR_INVALID_ARG;
+    StateView v;
+    QG_CHECK(spectra2d_ready(o, &v));
+    QG_HIP(hipSetDevice(v.device));
+    return spectra2d_record(o, out2d, iso);
+}
+
+static int iso_spectra_run(Owner o, int64_t first_step, int64_t nsteps, int64_t every, double *records,
+                           int64_t capacity, int64_t *nrecords) {
+    if (!o) return QG_ERR_INVALID_ARG;
+    int64_t n;
+    QG_CHECK(check_recorded(first_step, nsteps, every, records, capacity, &n));
+    StateView v;
+    QG_CHECK(spectra2d_ready(o, &v));
+    if (nrecords) *nrecords = n;
+    const size_t len = (size_t)v.nmembers * QG_SPEC_LINES * (size_t)qg_iso_shells(v.M, v.P);
+    QG_CHECK(run_recorded(first_step, nsteps, every, [&](int64_t t) { return o.step(t); }, [&](int64_t, int64_t k) {
+        return spectra2d_record(o, nullptr, records + len * (size_t)k);
+    }));
+    return o.finish(first_step + nsteps);
+}
+
 extern "C" {
+
+int qg_spectra2d(qg_ctx *c, double *out2d, double *iso) { return spectra2d_now(Owner{c, nullptr}, out2d, iso); }
+
+int qg_ens_spectra2d(qg_ens *e, double *out2d, double *iso) { return spectra2d_now(Owner{nullptr, e}, out2d, iso); }
+
+int qg_run_iso_spectra(qg_ctx *c, int64_t first_step, int64_t nsteps, int64_t every, double *records,
+                       int64_t capacity, int64_t *nrecords) {
+    return iso_spectra_run(Owner{c, nullptr}, first_step, nsteps, every, records, capacity, nrecords);
+}
+
+int qg_ens_run_iso_spectra(qg_ens *e, int64_t first_step, int64_t nsteps, int64_t every, double *records,
+                           int64_t capacity, int64_t *nrecords) {
+    return iso_spectra_run(Owner{nullptr, e}, first_step, nsteps, every, records, capacity, nrecords);
+}
+
+// ---- the pure host functions ------------------------------------------------------------------
 
 int qg_iso_shells(int64_t M, int64_t P) {
     if (!qg::spectra2d_supports(M, P)) return QG_ERR_UNSUPPORTED;

@@ -28,7 +28,7 @@
 #include <cstring>
 #include <new>
 
-#include "qg_tracer.hpp"
+#include "qg_owner.hpp"
 
 namespace qg {
 
@@ -356,8 +356,7 @@ int launch_advance(const TrcArgs &a, int nmembers, int form, hipStream_t s) {
 using namespace qg;
 
 struct qg_tracers {
-    qg_ctx *ctx = nullptr;  // the owner: one of the two
-    qg_ens *ens = nullptr;
+    Owner owner;
     int nt = 0;
     qg_tracer_params tp[QG_TRACERS_MAX];
     double *c = nullptr, *g = nullptr;
@@ -368,32 +367,30 @@ struct qg_tracers {
     double *part = nullptr;  // the diagnostics' partial records
     int device = 0;
 
-    void owner(TracerOwner *o) const {
-        if (ctx) tracer_owner(ctx, o);
-        else tracer_owner(ens, o);
-    }
-    size_t slot_off(const TracerOwner &o, int slot) const { return (size_t)slot * nt * o.F; }
+    size_t slot_off(const StateView &o, int slot) const { return (size_t)slot * nt * o.F; }
 };
 
-static bool aligned(const void *p, size_t n) { return reinterpret_cast<uintptr_t>(p) % n == 0; }
+// the header's rule: F64, one rank and no transport, no per-member physics, M and P >= 3
+static bool tracers_supported(const StateView &o) { return o.one_rank && o.f64 && o.uniform && o.M >= 3 && o.P >= 3; }
 
-static int tracers_create(qg_ctx *ctx, qg_ens *ens, int ntracers, const qg_tracer_params *tp, qg_tracers **out) {
+static const double *f64(const void *p) { return static_cast<const double *>(p); }
+
+static int tracers_create(Owner owner, int ntracers, const qg_tracer_params *tp, qg_tracers **out) {
     if (!out) return QG_ERR_INVALID_ARG;
     *out = nullptr;
-    if ((!ctx && !ens) || !tp || ntracers < 1 || ntracers > QG_TRACERS_MAX) return QG_ERR_INVALID_ARG;
+    if (!owner || !tp || ntracers < 1 || ntracers > QG_TRACERS_MAX) return QG_ERR_INVALID_ARG;
     for (int k = 0; k < ntracers; ++k)
         if ((tp[k].layer != 0 && tp[k].layer != 1) || tp[k].reserved != 0 || !std::isfinite(tp[k].kappa) ||
             !std::isfinite(tp[k].gamma) || tp[k].kappa < 0)
             return QG_ERR_INVALID_ARG;
     qg_tracers *t = new (std::nothrow) qg_tracers();
     if (!t) return QG_ERR_ALLOC;
-    t->ctx = ctx;
-    t->ens = ens;
+    t->owner = owner;
     t->nt = ntracers;
     std::memcpy(t->tp, tp, sizeof(qg_tracer_params) * (size_t)ntracers);
-    TracerOwner o;
-    t->owner(&o);
-    if (!o.supported) {
+    StateView o;
+    owner.view(&o);
+    if (!tracers_supported(o)) {
         delete t;
         return QG_ERR_UNSUPPORTED;
     }
@@ -409,15 +406,15 @@ static int tracers_create(qg_ctx *ctx, qg_ens *ens, int ntracers, const qg_trace
 }
 
 // the refusals of a call that reads the arrays, in the header's order
-static int tracers_ready(const qg_tracers *t, TracerOwner *o) {
+static int tracers_ready(const qg_tracers *t, StateView *o) {
     if (!t->c) return QG_ERR_NOT_BOUND;
-    t->owner(o);
-    if (!o->supported) return QG_ERR_UNSUPPORTED;  // (a transport attached since the create)
+    t->owner.view(o);
+    if (!tracers_supported(*o)) return QG_ERR_UNSUPPORTED;  // (a transport attached since the create)
     if (!o->bound || !t->ready) return QG_ERR_NOT_BOUND;
     return QG_OK;
 }
 
-static int tracers_record(qg_tracers *t, const TracerOwner &o, double *out) {
+static int tracers_record(qg_tracers *t, const StateView &o, double *out) {
     DiagArgs a{};
     a.M = (int)o.M;
     a.P = (int)o.P;
@@ -428,8 +425,8 @@ static int tracers_record(qg_tracers *t, const TracerOwner &o, double *out) {
     a.trc_stride = 3 * (size_t)t->nt * o.F;
     a.psi_stride = o.member_stride;
     a.dx = o.dx;
-    a.psi[0] = o.psi[0];
-    a.psi[1] = o.psi[1];
+    a.psi[0] = f64(o.psi[0]);
+    a.psi[1] = f64(o.psi[1]);
     a.c = t->c + t->slot_off(o, t->heads[0]);
     for (int k = 0; k < t->nt; ++k) a.layer[k] = t->tp[k].layer;
     a.part = t->part;
@@ -441,7 +438,7 @@ static int tracers_record(qg_tracers *t, const TracerOwner &o, double *out) {
     return QG_OK;
 }
 
-static int tracers_advance(qg_tracers *t, const TracerOwner &o) {
+static int tracers_advance(qg_tracers *t, const StateView &o) {
     TrcArgs a{};
     a.M = (int)o.M;
     a.P = (int)o.P;
@@ -454,8 +451,8 @@ static int tracers_advance(qg_tracers *t, const TracerOwner &o) {
     a.dx = o.dx;
     a.dt = o.dt;
     a.U = o.U;
-    a.psi[0] = o.psi[0];
-    a.psi[1] = o.psi[1];
+    a.psi[0] = f64(o.psi[0]);
+    a.psi[1] = f64(o.psi[1]);
     const int ch = t->heads[0], gh = t->heads[1], cn = (ch + 2) % 3, gn = (gh + 2) % 3;
     a.c_in = t->c + t->slot_off(o, ch);
     a.c_out = t->c + t->slot_off(o, cn);
@@ -482,11 +479,11 @@ static int tracers_advance(qg_tracers *t, const TracerOwner &o) {
 extern "C" {
 
 int qg_tracers_create(qg_ctx *owner, int ntracers, const qg_tracer_params *tp, qg_tracers **out) {
-    return tracers_create(owner, nullptr, ntracers, tp, out);
+    return tracers_create(Owner{owner, nullptr}, ntracers, tp, out);
 }
 
 int qg_ens_tracers_create(qg_ens *owner, int ntracers, const qg_tracer_params *tp, qg_tracers **out) {
-    return tracers_create(nullptr, owner, ntracers, tp, out);
+    return tracers_create(Owner{nullptr, owner}, ntracers, tp, out);
 }
 
 int qg_tracers_destroy(qg_tracers *t) {
@@ -510,9 +507,9 @@ int qg_tracers_bind(qg_tracers *t, double *c, double *g_store) {
 int qg_tracers_reset(qg_tracers *t) {
     if (!t) return QG_ERR_INVALID_ARG;
     if (!t->c) return QG_ERR_NOT_BOUND;
-    TracerOwner o;
-    t->owner(&o);
-    if (!o.supported) return QG_ERR_UNSUPPORTED;
+    StateView o;
+    t->owner.view(&o);
+    if (!tracers_supported(o)) return QG_ERR_UNSUPPORTED;
     QG_HIP(hipSetDevice(o.device));
     const size_t slot = (size_t)t->nt * o.F, blk = 3 * slot;
     for (int b = 0; b < o.nmembers; ++b) {
@@ -531,47 +528,39 @@ int qg_tracers_reset(qg_tracers *t) {
 
 int qg_tracers_advance(qg_tracers *t) {
     if (!t) return QG_ERR_INVALID_ARG;
-    TracerOwner o;
+    StateView o;
     QG_CHECK(tracers_ready(t, &o));
     return tracers_advance(t, o);
 }
 
 int qg_tracers_step(qg_tracers *t, int64_t timestep) {
     if (!t || timestep < 1) return QG_ERR_INVALID_ARG;
-    TracerOwner o;
+    StateView o;
     QG_CHECK(tracers_ready(t, &o));
     QG_CHECK(tracers_advance(t, o));
-    return t->ctx ? qg_step(t->ctx, timestep) : qg_ens_step(t->ens, timestep);
+    return t->owner.step(timestep);
 }
 
 int qg_tracers_run(qg_tracers *t, int64_t first_step, int64_t nsteps, int64_t every, double *records,
                    int64_t capacity, int64_t *nrecords) {
     if (!t || first_step < 1 || nsteps < 0) return QG_ERR_INVALID_ARG;
-    int64_t n = 0;
-    if (records) {
-        if (every < 1 || !aligned(records, 8)) return QG_ERR_INVALID_ARG;
-        n = nsteps / every;
-        if (capacity < n) return QG_ERR_INVALID_ARG;
-    }
-    TracerOwner o;
+    int64_t n = 0;  // (every and capacity count only with a record pointer)
+    if (records) QG_CHECK(check_recorded(first_step, nsteps, every, records, capacity, &n));
+    StateView o;
     QG_CHECK(tracers_ready(t, &o));
     if (nrecords) *nrecords = n;
     const size_t len = (size_t)o.nmembers * t->nt * QG_TRC_LINES;
-    int64_t k = 0;
-    for (int64_t s = first_step; s < first_step + nsteps; ++s) {
-        QG_CHECK(qg_tracers_step(t, s));
-        if (records && (s - first_step + 1) % every == 0) {
-            t->owner(&o);  // the newest psi slot has moved
-            QG_CHECK(tracers_record(t, o, records + len * (size_t)k++));
-        }
-    }
-    // as qg_run / qg_ens_run end (a context: a failed deferred PCG certificate is reported here)
-    return t->ctx ? qg_run(t->ctx, first_step + nsteps, 0) : qg_ens_run(t->ens, first_step + nsteps, 0);
+    QG_CHECK(run_recorded(first_step, nsteps, records ? every : 0, [&](int64_t s) { return qg_tracers_step(t, s); },
+                          [&](int64_t, int64_t k) {
+                              t->owner.view(&o);  // the newest psi slot has moved
+                              return tracers_record(t, o, records + len * (size_t)k);
+                          }));
+    return t->owner.finish(first_step + nsteps);
 }
 
 int qg_tracers_diagnostics(qg_tracers *t, double *out) {
     if (!t || !out || !aligned(out, 8)) return QG_ERR_INVALID_ARG;
-    TracerOwner o;
+    StateView o;
     QG_CHECK(tracers_ready(t, &o));
     QG_HIP(hipSetDevice(o.device));
     return tracers_record(t, o, out);

@@ -188,6 +188,41 @@ def test_pcg_context_gives_the_spectral_contexts_bytes(env):
     a.close(), b.close()
 
 
+def stepped_record(qg, mode):
+    """The records of a 64 x 16 context in keep-order mode `mode` (0: rotating) after three whole
+    steps and after the next qg_evolve_zeta alone, with the physical slot of the newest zeta then."""
+    st = qg.State(qg.bench_model(64, P=16)).initialise()
+    if mode:
+        st.set_keep_order(True, slot1_only=mode >= 2, deferred=mode == 3)
+    for t in range(1, 4):
+        st.evolve_zeta_(t)
+        st.evolve_psi_()
+    whole = st.spectra()
+    st.evolve_zeta_(4)
+    half, slot = st.spectra(), st.slot("zeta", 1)
+    st.synchronize()
+    out = whole.cpu().numpy().tobytes(), half.cpu().numpy().tobytes(), slot
+    st.close()
+    return out
+
+
+@pytest.fixture(scope="module")
+def rotating_record(env):
+    return stepped_record(env[1], 0)
+
+
+@pytest.mark.parametrize("mode", [1, 2, 3])
+def test_every_keep_order_mode_reads_the_newest_slot(env, rotating_record, mode):
+    """Rotating, keep-order, slot-1 and slot-1-deferred contexts hold the same newest state in
+    different physical slots: the record's bytes are the rotating context's.  Between the tendency
+    and the solve the deferred mode keeps the newest zeta in physical slot 2 (heads[0] == 1)."""
+    whole, half, slot = stepped_record(env[1], mode)
+    assert rotating_record[2] == 2 and slot == (1 if mode == 3 else 0)
+    assert np.frombuffer(whole).max() > 0 and whole != half
+    assert whole == rotating_record[0]
+    assert half == rotating_record[1]
+
+
 # ---- 7. ensemble = single, bit for bit ----------------------------------------------------------
 def members_equal_single(torch, qg, ens):
     """Every member's record against qg_spectra of one qg_ctx bound, member after member, to a
@@ -308,6 +343,21 @@ def test_a_capacity_one_short_is_refused_and_leaves_the_state(env, plain_run):
 
 
 # ---- 9. refusals with a live handle -------------------------------------------------------------
+def test_refused_once_a_transport_is_attached(env):
+    torch, qg = env
+    L, K = qg.lib(), qg._lib
+    out = torch.zeros((2 * 5 * 33,), dtype=torch.float64, device="cuda")
+    n = C.c_int64(-7)
+    st = qg.State(qg.bench_model(64, P=5)).initialise()
+    ag, sr = K.AllgatherFn(lambda *a: 0), K.SendrecvFn(lambda *a: 0)
+    assert L.qg_comm_init_host(st._ctx, 1, 0, ag, sr, None) == K.QG_OK
+    assert L.qg_spectra(st._ctx, out.data_ptr()) == K.QG_ERR_UNSUPPORTED
+    assert L.qg_run_spectra(st._ctx, 1, 2, 1, out.data_ptr(), 2, C.byref(n)) == K.QG_ERR_UNSUPPORTED
+    st.close()
+    torch.cuda.synchronize()
+    assert n.value == -7 and not out.any(), "a refused call writes nothing"
+
+
 def test_refusals_with_a_live_handle(env):
     torch, qg = env
     L, K = qg.lib(), qg._lib

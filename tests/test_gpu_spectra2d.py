@@ -216,6 +216,42 @@ def test_f32_context_gives_the_bytes_of_the_widened_state(env):
     a.close(), b.close()
 
 
+def stepped_record(qg, mode):
+    """The (2-D, isotropic) records of a 64 x 16 context in keep-order mode `mode` (0: rotating)
+    after three whole steps and after the next qg_evolve_zeta alone, with the physical slot of the
+    newest zeta then."""
+    st = qg.State(qg.bench_model(64, P=16)).initialise()
+    if mode:
+        st.set_keep_order(True, slot1_only=mode >= 2, deferred=mode == 3)
+    for t in range(1, 4):
+        st.evolve_zeta_(t)
+        st.evolve_psi_()
+    whole = st.spectra2d(full=True)
+    st.evolve_zeta_(4)
+    half, slot = st.spectra2d(full=True), st.slot("zeta", 1)
+    st.synchronize()
+    out = tuple(b"".join(r.cpu().numpy().tobytes() for r in pair) for pair in (whole, half)) + (slot,)
+    st.close()
+    return out
+
+
+@pytest.fixture(scope="module")
+def rotating_record(env):
+    return stepped_record(env[1], 0)
+
+
+@pytest.mark.parametrize("mode", [1, 2, 3])
+def test_every_keep_order_mode_reads_the_newest_slot(env, rotating_record, mode):
+    """Rotating, keep-order, slot-1 and slot-1-deferred contexts hold the same newest state in
+    different physical slots: the records' bytes are the rotating context's.  Between the tendency
+    and the solve the deferred mode keeps the newest zeta in physical slot 2 (heads[0] == 1)."""
+    whole, half, slot = stepped_record(env[1], mode)
+    assert rotating_record[2] == 2 and slot == (1 if mode == 3 else 0)
+    assert np.frombuffer(whole).max() > 0 and whole != half
+    assert whole == rotating_record[0]
+    assert half == rotating_record[1]
+
+
 def members_equal_single(torch, qg, ens, which=None):
     """Members' records (all, or those of `which`) against qg_spectra2d of one qg_ctx bound, member
     after member, to a copy of that member's block; and iso without the 2-D record is the same."""
