@@ -1,7 +1,10 @@
 """A numpy restatement of the multigrid preconditioner of csrc/qg_mg.hip (QG_PRECOND_MULTIGRID)
 and of the PCG around it (csrc/qg_pcg.hip) -- test infrastructure: the CPU suite checks the
 design (symmetry, grid-independent iteration counts, the slab form's equality with the global
-cycle) without a GPU; the GPU tests check the kernels against the C oracle.
+cycle) without a GPU; tests/test_gpu_mg_geometry.py holds the kernels to this model run in long
+double after one and three PCG iterations, tests/test_gpu_mg.py holds the converged solve to the
+direct solvers.  Every function keeps the dtype of its fields (float64 or np.longdouble); the
+scalars dx, alpha, cx, cy, omega / diag stay the float64 values the device uses.
 
 Operator per level: B = -(cx (E + W - 2) + cy (N + S - 2) + alpha), x periodic, y periodic on
 the global grid.  V(2,2): damped Jacobi (omega 0.8) from zero, full-weighting restriction,
@@ -69,11 +72,11 @@ def _prolong(e, rx, ry, above=None):
     """Bilinear interpolation; above: the slab's coarse ghost row P_c (None: y wraps)."""
     if ry:
         nxt = np.roll(e, -1, 0) if above is None else np.vstack([e[1:], above[None]])
-        f = np.zeros((2 * e.shape[0], e.shape[1]))
+        f = np.zeros((2 * e.shape[0], e.shape[1]), dtype=e.dtype)
         f[0::2], f[1::2] = e, 0.5 * (e + nxt)
         e = f
     if rx:
-        f = np.zeros((e.shape[0], 2 * e.shape[1]))
+        f = np.zeros((e.shape[0], 2 * e.shape[1]), dtype=e.dtype)
         f[:, 0::2], f[:, 1::2] = e, 0.5 * (e + np.roll(e, -1, 1))
         e = f
     return e
@@ -170,23 +173,23 @@ def pcg(b, dx, al, pinned, G=1, rtol=1e-13, maxit=200):
     if pinned:
         r[0, 0] = 0.0
     x = np.zeros_like(b)
-    bb = float((r * r).sum())
+    bb = (r * r).sum()
     z = precond(r, dx, al, pinned, G)
     if pinned:
         z[0, 0] = r[0, 0]
-    p, rz, hist = z.copy(), float((r * z).sum()), []
+    p, rz, hist = z.copy(), (r * z).sum(), []
     for it in range(1, maxit + 1):
         q = pinned_apply(p, dx, al, pinned)
-        a = rz / float((p * q).sum())
+        a = rz / (p * q).sum()
         x += a * p
         r -= a * q
-        hist.append(np.sqrt(float((r * r).sum()) / bb))
+        hist.append(np.sqrt((r * r).sum() / bb))
         if hist[-1] <= rtol:
             return x, it, hist
         z = precond(r, dx, al, pinned, G)
         if pinned:
             z[0, 0] = r[0, 0]
-        rz2 = float((r * z).sum())
+        rz2 = (r * z).sum()
         p = z + (rz2 / rz) * p
         rz = rz2
     return x, maxit, hist
