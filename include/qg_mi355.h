@@ -105,7 +105,7 @@ typedef struct qg_params {
     int32_t pcg_maxit;  /* default 500                                                  */
     int32_t chunk_rows; /* y-chunk of the spectral solver; 0 = automatic                */
     int32_t dtype;      /* qg_dtype of the state arrays (default QG_F64; QG_F32 needs   *
-                         * QG_SOLVER_SPECTRAL)                                          */
+                         * QG_SOLVER_SPECTRAL and an even M)                            */
     int32_t reserved0;
     /* Double-gyre wind forcing of the upper layer (an extension: the reference has no wind
      * term; BASELINE config 1 names one).  With wind_tau0 != 0, zeta_f1 gains a last term

@@ -498,7 +498,11 @@ def diagnostics(zeta, psi, dx):
     """The monitoring record of qg_diagnostics from (M+2, P+2, 2, 3) arrays, slot 1 (newest):
     update_max / update_min of each layer (run_model.jl:41-53, starting from -Inf / +Inf) and
     the definitional sums (circulation, enstrophy, forward-difference kinetic energy,
-    interface term) -- not part of the reference, so parity unpinned beyond the max / min."""
+    interface term) -- not part of the reference, so parity unpinned beyond the max / min.
+    The max / min are taken over the whole array, ghost ring included, as run_model.jl takes
+    them; qg_diagnostics reads the interior only (its header's contract).  The two agree on
+    every stepped state, whose ring is the periodic copy of the interior, and only there:
+    tests/diag_model.py's exact() is the interior record."""
     out = {k: [0.0, 0.0] for k in ("zeta_max", "zeta_min", "psi_max", "psi_min", "zeta_sum",
                                    "enstrophy", "energy")}
     for l in range(2):
