@@ -363,6 +363,35 @@ enum { QG_TEND_AUTO = 0, QG_TEND_RING = 1, QG_TEND_DIRECT = 2, QG_TEND_ONE_POINT
  * the two-points-per-thread pair kernel (size rule otherwise).  All forms are bit-identical. */
 int qg_set_form(int which, int value);
 int qg_get_form(int which);
+/* The launch of one tendency as the library would issue it, under the current qg_set_form state:
+ * which kernel form, its strip width and workgroup size, and the grid.  Pure host function (no
+ * device needed; a test checks the launch rules for any shape): what the library asks the device
+ * -- how many workgroups of the chosen kernel the chip holds at once -- is the argument
+ * `resident` (>= 1; only the balanced launches use it).
+ * M: interior columns; rows = {j0, j1, j2, j3}: the output rows [j0, j1) and an optional second
+ * range [j2, j3) (empty: j3 <= j2); esize: 8 (F64) or 4 (F32 state); cert != 0: the certifying
+ * tendency of the PCG path (F64), refused with QG_ERR_INVALID_ARG when it would write more than
+ * `cap` workgroups' partials; nmembers = 0: a single context, >= 1: the ensemble launch (F64, one
+ * row range), refused with QG_ERR_UNSUPPORTED from 2^31 workgroups on.  A launch with no rows is
+ * not made: blocks = 0.                                                                      */
+enum { QG_TEND_KERNEL_RING = 0, QG_TEND_KERNEL_PAIR = 1, QG_TEND_KERNEL_DIRECT = 2 };
+typedef struct qg_tend_plan {
+    int32_t kernel;    /* QG_TEND_KERNEL_*: LDS ring (one point per thread), two points per    *
+                        * thread, cache-resident one-point                                     */
+    int32_t width;     /* columns per workgroup (the strip width W; direct: 64)                */
+    int32_t threads;   /* per workgroup (the certifying ring: 2 W, both layers)                */
+    int32_t rows;      /* rows per workgroup where that is fixed (tile R, 8, direct: 4);       *
+                        * 0: the balanced split below                                          */
+    int32_t chipfulls; /* balanced: rows split so the grid is about this many times `resident` */
+    int32_t nx;        /* column strips                                                        */
+    int32_t nyA, nyB;  /* row workgroups of the two row ranges                                 */
+    int32_t nz;        /* layers across the grid: 2, or 1 where a workgroup holds both (cert)  */
+    int32_t reserved;
+    int64_t blocks;    /* workgroups launched: nx (nyA + nyB) nz; members: that times nmembers, *
+                        * as one linear grid                                                   */
+} qg_tend_plan;
+int qg_tendency_plan(int64_t M, const int rows[4], int esize, int cert, int nmembers, int resident,
+                     int64_t cap, qg_tend_plan *out);
 
 /* ---- stateless kernels on (M+2, P+2) device fields (ghost ring refreshed on output) ---- */
 int qg_laplace_5p(const double *u, double *out, int64_t M, int64_t P, double dx, void *stream); /* laplacian.jl:15-27 */

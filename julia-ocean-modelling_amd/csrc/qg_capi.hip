@@ -14,6 +14,7 @@
 #include "qg_owner.hpp"
 #include "qg_pcg.hpp"
 #include "qg_spectral.hpp"
+#include "qg_tend_plan.hpp"
 
 namespace qg {
 static std::atomic<int> g_form[QG_FORM_COUNT];  // qg_set_form (zero-initialised: automatic)
@@ -159,8 +160,9 @@ int qg_set_form(int which, int value) {
     if (which == QG_FORM_TENDENCY && value > QG_TEND_ONE_POINT) return QG_ERR_INVALID_ARG;
     if ((which == QG_FORM_ROW_SPLIT || which == QG_FORM_PCG_NO_CERTIFICATE) && value > 1) return QG_ERR_INVALID_ARG;
     if (which == QG_FORM_TENDENCY_TILE && value != 0) {
-        const int w = value >> 16, r = value & 0xffff;
-        if ((w != 64 && w != 128 && w != 256 && w != 512) || r < 1) return QG_ERR_INVALID_ARG;
+        int w, r;
+        qg::tend_tile(value, w, r);
+        if (!w) return QG_ERR_INVALID_ARG;
     }
     qg::g_form[which].store(value, std::memory_order_relaxed);
     return QG_OK;
@@ -401,16 +403,6 @@ int qg_set_slots(qg_ctx *c, const int heads[3]) {
     return QG_OK;
 }
 
-extern "C++" {
-template <class T>
-static void fill_wrap_rows(const qg_ctx *c, const T *base, RowSrcT<T> &rs) {
-    // single-GPU: rows -2,-1,P,P+1 are the periodic images P-2,P-1,0,1
-    const int64_t P = c->p.P, ld = c->p.M + 2;
-    const int64_t rows[4] = {(P - 2 + P) % P, P - 1, 0, 1 % P};
-    for (int h = 0; h < 4; ++h) rs.halo[h] = base + fidx(1, rows[h] + 1, ld);
-}
-}  // extern "C++"
-
 // ---- multi-GPU ghost rows --------------------------------------------------------------
 // A step's exchange carries only the tendency's halo rows; the ghost rows (memory rows 0 and
 // P+1, the drop-in ghost ring) of every field a step writes are left stale -- no kernel reads
@@ -473,20 +465,7 @@ static int evolve_zeta_t(qg_ctx *c, int64_t timestep) {
         fh2 = fuse_fshift ? 1 : 2;
         fn = 0;
     }
-    TendArgsT<T> a{};
-    a.M = p.M;
-    a.P = p.P;
-    a.ld = p.M + 2;
-    a.dx = p.dx;
-    a.visc = p.visc;
-    a.dt = p.dt;
-    a.U = p.U;
-    a.r = p.r;
-    a.beta[0] = c->d.beta1;
-    a.beta[1] = c->d.beta2;
-    a.ab3 = timestep >= 3;
-    a.j0 = 0;
-    a.j1 = (int)p.P;
+    TendArgsT<T> a = tend_model_args<T>(p, p.visc, p.U, p.r, c->d.beta1, c->d.beta2, timestep);
     a.write_ghost_rows = !c->distributed;
     QG_CHECK(ensure_wind(c));
     a.wind = c->wind;
@@ -503,10 +482,7 @@ static int evolve_zeta_t(qg_ctx *c, int64_t timestep) {
         }
     }
     if (!c->distributed) {
-        for (int l = 0; l < 2; ++l) {
-            fill_wrap_rows(c, a.zeta[l], a.zeta_rows[l]);
-            fill_wrap_rows(c, a.psi[l], a.psi_rows[l]);
-        }
+        tend_wrap_rows(a);
         bool done = false;
         if constexpr (std::is_same<T, double>::value) {
             // the previous solve's deferred PCG certification rides in this tendency (it reads

@@ -188,7 +188,7 @@ inline Derived derive(const qg_params &m) {
     return d;
 }
 
-// ---- stencil / tendency launchers (qg_stencil.hip) ----------------------------------
+// ---- stencil (qg_ops.hip) and tendency (qg_tend_launch.hip) launchers ---------------
 // T = element type of the state fields (double: the reference's Float64; float: the F32
 // build of BASELINE config 5)
 template <class T>
@@ -232,6 +232,39 @@ struct TendArgsT {
     int cert_pin;              // system 0 pinned at interior (0, 0)
 };
 using TendArgs = TendArgsT<double>;
+
+// The model half of a step's TendArgsT -- sizes, constants, all rows [0, P) as one range -- for
+// the step `timestep` (1-based: AB3 from the third on); the caller adds the field pointers.
+template <class T>
+inline TendArgsT<T> tend_model_args(const qg_params &p, double visc, double U, double r, double beta1, double beta2,
+                                    int64_t timestep) {
+    TendArgsT<T> a{};
+    a.M = p.M;
+    a.P = p.P;
+    a.ld = p.M + 2;
+    a.dx = p.dx;
+    a.visc = visc;
+    a.dt = p.dt;
+    a.U = U;
+    a.r = r;
+    a.beta[0] = beta1;
+    a.beta[1] = beta2;
+    a.ab3 = timestep >= 3;
+    a.j0 = 0;
+    a.j1 = (int)p.P;
+    return a;
+}
+// One rank: rows -2, -1, P, P+1 of zeta and psi are the periodic images P-2, P-1, 0, 1 of the
+// fields a.zeta / a.psi themselves
+template <class T>
+inline void tend_wrap_rows(TendArgsT<T> &a) {
+    const int64_t P = a.P, rows[4] = {(P - 2 + P) % P, P - 1, 0, 1 % P};
+    for (int l = 0; l < 2; ++l)
+        for (int h = 0; h < 4; ++h) {
+            a.zeta_rows[l].halo[h] = a.zeta[l] + fidx(1, rows[h] + 1, a.ld);
+            a.psi_rows[l].halo[h] = a.psi[l] + fidx(1, rows[h] + 1, a.ld);
+        }
+}
 
 // double-gyre wind forcing of local row j of a slab at global row offset j0 (qg_params)
 inline double wind_row(double tau0, double rho0, double H1, double dx, int64_t P_total, int64_t jg) {

@@ -279,25 +279,10 @@ static int ens_evolve_zeta(qg_ens *e, int64_t timestep) {
     const qg_params &p = e->p;
     const int zh = e->heads[0], ph = e->heads[1], fh = e->heads[2], fh2 = (fh + 1) % 3;
     const int zn = (zh + 2) % 3, fn = (fh + 2) % 3;
-    TendArgs a{};
-    a.M = p.M;
-    a.P = p.P;
-    a.ld = p.M + 2;
-    a.dx = p.dx;
-    a.visc = e->mp[0].visc;  // member 0's: every member's, unless e->rec carries their own
-    a.dt = p.dt;
-    a.U = e->mp[0].U;
-    a.r = e->mp[0].r;
-    a.beta[0] = e->d.beta1;
-    a.beta[1] = e->d.beta2;
-    a.ab3 = timestep >= 3;
-    a.j0 = 0;
-    a.j1 = (int)p.P;
+    // member 0's (visc, U, r): every member's, unless e->rec carries their own
+    TendArgs a = tend_model_args<double>(p, e->mp[0].visc, e->mp[0].U, e->mp[0].r, e->d.beta1, e->d.beta2, timestep);
     a.write_ghost_rows = 1;
     a.wind = e->wind;
-    // rows -2, -1, P, P+1 are the periodic images P-2, P-1, 0, 1
-    const int64_t P = p.P, ld = p.M + 2;
-    const int64_t rows[4] = {(P - 2 + P) % P, P - 1, 0, 1 % P};
     for (int l = 0; l < 2; ++l) {
         a.zeta[l] = e->field(e->zeta, l, zh);
         a.psi[l] = e->field(e->psi, l, ph);
@@ -305,11 +290,8 @@ static int ens_evolve_zeta(qg_ens *e, int64_t timestep) {
         a.fprev2[l] = e->field(e->fst, l, fh2);
         a.zeta_out[l] = e->field(e->zeta, l, zn);
         a.f_out[l] = e->field(e->fst, l, fn);
-        for (int h = 0; h < 4; ++h) {
-            a.zeta_rows[l].halo[h] = a.zeta[l] + fidx(1, rows[h] + 1, ld);
-            a.psi_rows[l].halo[h] = a.psi[l] + fidx(1, rows[h] + 1, ld);
-        }
     }
+    tend_wrap_rows(a);
     if (e->rec) QG_CHECK(launch_tendency_sweep(a, e->nmembers, (int64_t)e->member_stride(), e->rec, e->stream));
     else QG_CHECK(launch_tendency_members(a, e->nmembers, (int64_t)e->member_stride(), e->stream));
     e->heads[0] = zn;

@@ -29,6 +29,7 @@
 #include <new>
 
 #include "qg_owner.hpp"
+#include "qg_tend_dev.hpp"
 
 namespace qg {
 
@@ -64,21 +65,8 @@ struct TrcArgs {
     int list[2][NTMAX];      // their indices, ascending
 };
 
-// J at one point from accessors Z(a,b), S(a,b) (arakawa.jl:7-62, same evaluation order; the
-// expression of qg_stencil.hip's arakawa_point)
-template <class ZF, class SF>
-__device__ __forceinline__ double arakawa_point(ZF Z, SF S, double den) {
-    const double jpp = (Z(1, 0) - Z(-1, 0)) * (S(0, 1) - S(0, -1)) - (Z(0, 1) - Z(0, -1)) * (S(1, 0) - S(-1, 0));
-    const double jpt = ((Z(1, 0) * (S(1, 1) - S(1, -1)) - Z(-1, 0) * (S(-1, 1) - S(-1, -1))) -
-                        Z(0, 1) * (S(1, 1) - S(-1, 1))) +
-                       Z(0, -1) * (S(1, -1) - S(-1, -1));
-    const double jtp = ((Z(1, 1) * (S(0, 1) - S(1, 0)) - Z(-1, -1) * (S(-1, 0) - S(0, -1))) -
-                        Z(-1, 1) * (S(0, 1) - S(-1, 0))) +
-                       Z(1, -1) * (S(1, 0) - S(0, -1));
-    return ((jpp + jpt) + jtp) / den;
-}
-
-// G of tracer k at one point from accessors Z (c_k) and S (psi_l)
+// G of tracer k at one point from accessors Z (c_k) and S (psi_l); J is the tendency's own
+// arakawa_point (qg_tend_dev.hpp)
 template <class ZF, class SF>
 __device__ __forceinline__ double tracer_G(const TrcArgs &a, int k, bool upper, ZF Z, SF S) {
     const double idx = 1.0 / a.dx, idx2 = idx * idx, cdc = 0.5 * idx, den = 12.0 * (a.dx * a.dx);

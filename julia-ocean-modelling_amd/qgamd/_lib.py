@@ -40,6 +40,7 @@ QG_KEEP_ORDER_SLOT1, QG_KEEP_ORDER_SLOT1_DEFERRED = 2, 3
 # qg_set_form (kernel-form selection, process-wide; 0 = automatic)
 QG_FORM_TENDENCY, QG_FORM_TENDENCY_TILE, QG_FORM_ROW_SPLIT, QG_FORM_PCG_NO_CERTIFICATE = 0, 1, 2, 3
 QG_TEND_AUTO, QG_TEND_RING, QG_TEND_DIRECT, QG_TEND_ONE_POINT = 0, 1, 2, 3
+QG_TEND_KERNEL_RING, QG_TEND_KERNEL_PAIR, QG_TEND_KERNEL_DIRECT = 0, 1, 2
 
 
 class QgParams(C.Structure):
@@ -88,6 +89,14 @@ class QgTracerParams(C.Structure):
     1), diffusivity and imposed mean meridional gradient."""
 
     _fields_ = [("layer", C.c_int32), ("reserved", C.c_int32), ("kappa", C.c_double), ("gamma", C.c_double)]
+
+
+class QgTendPlan(C.Structure):
+    """Mirror of ``struct qg_tend_plan``: qg_tendency_plan's launch of one tendency."""
+
+    _fields_ = [("kernel", C.c_int32), ("width", C.c_int32), ("threads", C.c_int32), ("rows", C.c_int32),
+                ("chipfulls", C.c_int32), ("nx", C.c_int32), ("nyA", C.c_int32), ("nyB", C.c_int32),
+                ("nz", C.c_int32), ("reserved", C.c_int32), ("blocks", C.c_int64)]
 
 
 class QgStats(C.Structure):
@@ -145,6 +154,8 @@ SIGNATURES = [
     ("qg_solver_destroy", C.c_int, [_vp]),
     ("qg_set_form", C.c_int, [C.c_int, C.c_int]),
     ("qg_get_form", C.c_int, [C.c_int]),
+    ("qg_tendency_plan", C.c_int, [_i64, C.c_int * 4, C.c_int, C.c_int, C.c_int, C.c_int, _i64,
+                                   C.POINTER(QgTendPlan)]),
     ("qg_laplace_5p", C.c_int, [_dp, _dp, _i64, _i64, C.c_double, _vp]),
     ("qg_cd", C.c_int, [_dp, _dp, _i64, _i64, C.c_double, _vp]),
     ("qg_arakawa_J", C.c_int, [_dp, _dp, _dp, _i64, _i64, C.c_double, _vp]),

@@ -1,5 +1,7 @@
-"""Which strip bodies a launch of the LDS-ring tendency kernels reaches, restated in Python from
-csrc/qg_stencil.hip, and the case lists of tests/test_gpu_tendency_geometry.py.
+"""Which kernel and grid a tendency launch gets (plan(): csrc/qg_tend_plan.hpp restated; the CPU
+test compares it with the library's qg_tendency_plan case by case), which strip bodies a launch
+of the LDS-ring kernels reaches, restated from csrc/qg_tend_ring.hip and csrc/qg_tend_pair.hip,
+and the case lists of tests/test_gpu_tendency_geometry.py.
 
 The ring kernels (`tendency_kernel`, `tendency_pair_kernel`, the certifying
 `tendency_kernel<128, 1, double, true>`) give each workgroup a strip of W columns starting at
@@ -15,9 +17,9 @@ compiled bodies:
 
 Row groups: a range of nr rows starting at r0 is split over ny workgroups,
 jb0 = r0 + yy * nr // ny, jb1 = r0 + (yy + 1) * nr // ny.  With a forced tile
-(qg_set_form(QG_FORM_TENDENCY_TILE, (W << 16) | R), launch_tend_variant) ny = ceil(nr / R); in
-the balanced launches (launch_tend_balanced, launch_tend_pair, launch_tendency_cert_t)
-ny = max(1, min(nr // 4, target * nr // (rA + rB))) with target = the resident workgroups of
+(qg_set_form(QG_FORM_TENDENCY_TILE, (W << 16) | R)) ny = ceil(nr / R); in the balanced launches
+(tend_grid of csrc/qg_tend_plan.hpp with no fixed rows: the 256-point ring, the pair kernel, the
+certifying ring) ny = max(1, min(nr // 4, target * nr // (rA + rB))) with target = the resident workgroups of
 a few chip-fulls per column strip (waves * CUs * occupancy / (2 nx), or 3 * CUs * occupancy /
 nx for the certifying kernel): a property of the device.  ny = max(1, nr // 4) whenever
 target * nr // (rA + rB) >= nr // 4 -- for one row range, target >= nr // 4.  The lists below
@@ -33,7 +35,7 @@ may touch them: slab_launches() gives the ranges, slab_classes() what they reach
 
 An empty row group (jb0 >= jb1, the kernels' early return) needs ny > nr.  No launch produces
 one: ceil(nr / R) <= nr for R >= 1, and max(1, nr // 4) <= nr for nr >= 1; a range with no rows
-gets no workgroups (nB = 0) and a launch with no rows at all is not made (launch_tendency_t).
+gets no workgroups (nyB = 0) and a launch with no rows at all is not made (launch_tendency).
 The class is modelled (a hand-made ny shows it) but no case list can reach it.
 """
 
@@ -59,13 +61,75 @@ def ceil_div(a, b):
 
 
 def tile_ny(nr, R):
-    """launch_tend_variant: row workgroups of a range of nr rows, about R rows each."""
+    """Fixed rows per workgroup: row workgroups of a range of nr rows, about R rows each."""
     return ceil_div(nr, R) if nr > 0 else 0
 
 
 def balanced_ny(nr, total_rows, target=1 << 20):
-    """The `split` of launch_tend_balanced / launch_tend_pair / launch_tendency_cert_t."""
+    """The `split` of the balanced launches (tend_grid)."""
     return 0 if nr <= 0 else max(1, min(nr // 4, target * nr // total_rows))
+
+
+# ---- the launch plan (csrc/qg_tend_plan.hpp: tend_choose, tend_grid) ------------------------
+RING, PAIR, DIRECT = 0, 1, 2                                  # QG_TEND_KERNEL_*
+FORM_AUTO, FORM_RING, FORM_DIRECT, FORM_ONE_POINT = 0, 1, 2, 3  # QG_TEND_*
+OK, INVALID_ARG, UNSUPPORTED = 0, -1, -2
+TEND_DIRECT_PTS, CERT_DIRECT_PTS = 1.2e6, 0.5e6
+PLAN_FIELDS = ("kernel", "width", "threads", "rows", "chipfulls", "nx", "nyA", "nyB", "nz", "blocks")
+
+
+def tile_of(v):
+    """(W, R) of a QG_FORM_TENDENCY_TILE value, W = 0 where the default geometry applies."""
+    w, r = v >> 16, v & 0xffff
+    return (w, r) if w in (64, 128, 256, 512) and r >= 1 else (0, r)
+
+
+def plan(M, rows, esize=8, cert=False, nmembers=0, form=FORM_AUTO, tile=0, resident=1280, cap=1 << 40):
+    """(status, plan) of the launch of rows = (j0, j1, j2, j3): the form-selection rule and the
+    grid, as qg_tendency_plan reports them.  plan: PLAN_FIELDS (None unless status is OK)."""
+    j0, j1, j2, j3 = rows
+    rA, rB = max(0, j1 - j0), (j3 - j2 if j3 > j2 else 0)
+    if M < 1 or esize not in (8, 4) or nmembers < 0 or ((cert or nmembers) and esize != 8):
+        return INVALID_ARG, None
+    pts = float(M) * (rA + rB)
+    nz, fixed, chipfulls = 2, 0, 0
+    if nmembers:
+        if cert or rA <= 0 or rB > 0:
+            return INVALID_ARG, None
+        kernel, W, fixed = DIRECT, 64, 4
+    elif cert:
+        nz = 1
+        if form == FORM_DIRECT or (form != FORM_RING and pts < CERT_DIRECT_PTS):
+            kernel, W, fixed = DIRECT, 64, 4
+        else:
+            kernel, W, chipfulls = RING, 128, 3
+    elif tile_of(tile)[0]:
+        kernel, (W, fixed) = RING, tile_of(tile)
+    elif esize == 4 and form == FORM_AUTO and M % 2 == 0:
+        kernel, W, chipfulls = PAIR, 512, (20 if pts >= 40.0e6 else 2)
+    elif form == FORM_DIRECT or (form != FORM_RING and pts < TEND_DIRECT_PTS):
+        kernel, W, fixed = DIRECT, 64, 4
+    elif 0.75e6 <= pts < 3.0e6:
+        kernel, W, fixed = RING, 128, 8
+    else:
+        kernel, W = RING, 256
+        chipfulls = 16 if pts >= 40.0e6 else 9 if pts >= 12.0e6 else 1 if pts >= 3.0e6 else 2
+    threads = 256 if kernel != RING else (2 * W if cert else W)
+    nx = ceil_div(M, W)
+    if fixed:
+        nyA, nyB = tile_ny(rA, fixed), tile_ny(rB, fixed)
+    else:
+        target = max(1, chipfulls * resident // (nz * nx))
+        nyA, nyB = balanced_ny(rA, rA + rB, target), balanced_ny(rB, rA + rB, target)
+    blocks = nx * (nyA + nyB) * nz * max(1, nmembers)
+    p = dict(zip(PLAN_FIELDS, (kernel, W, threads, fixed, chipfulls, nx, nyA, nyB, nz, blocks)))
+    if nmembers:
+        return (UNSUPPORTED, None) if blocks > 0x7fffffff else (OK, p)
+    if nyA + nyB > 65535:
+        return UNSUPPORTED, None
+    if cert and blocks > cap:
+        return INVALID_ARG, None
+    return OK, p
 
 
 def row_groups(r0, nr, ny):
@@ -120,7 +184,7 @@ def cert_classes(M, P):
 
 
 def balanced_classes(M, P):
-    """QG_TEND_RING without a tile (F64, 256-point strips), where launch_tendency_t takes the
+    """QG_TEND_RING without a tile (F64, 256-point strips), where the planner takes the
     balanced geometry (below 0.75 M points)."""
     return classes(256, M, P, [(0, P, balanced_ny(P, P))])
 

@@ -1,4 +1,4 @@
-"""Every strip geometry of the ring tendency kernels (csrc/qg_stencil.hip), bit for bit, at the
+"""Every strip geometry of the ring tendency kernels (csrc/qg_tend_ring.hip, csrc/qg_tend_pair.hip), bit for bit, at the
 smallest shapes that reach each body (tests/tend_geometry.py has the dispatch model and the
 case lists; tests/test_tendency_geometry_cpu.py proves the lists reach every body).
 
@@ -203,7 +203,7 @@ def test_certifying_tendency_states_and_counts(env, M, P):
 
 
 def _relres_numpy(R, m, zeta, psi):
-    """The certificate's definition (qg_stencil.hip, CERT; qg_pcg.hip cert_latch) on (M+2, P+2)
+    """The certificate's definition (qg_tend_ring.hip, CERT; qg_pcg.hip cert_latch) on (M+2, P+2)
     fields with their periodic ring: b_s = -(P_inv zeta)_s, r_s = b_s + lap(psi~_s) +
     alpha_s psi~_s with psi~ = P_fwd^-1 psi, alpha = (0, S_eig), b = r = 0 at the pinned point
     of system 0; sqrt(sum r^2 / sum b^2) per system."""

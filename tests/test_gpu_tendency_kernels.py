@@ -1,5 +1,5 @@
 """The two tendency kernels (the LDS-ring kernel for large grids, the cache-resident one for
-grids below ~1.2 M points, csrc/qg_stencil.hip) evaluate the same expressions in the same
+grids below ~1.2 M points; csrc/qg_tend_ring.hip, csrc/qg_tend_direct.hip) evaluate the same expressions in the same
 order: forced one way and the other (qg_set_form(QG_FORM_TENDENCY, QG_TEND_RING / _DIRECT)),
 five Euler + AB3 steps give bit-identical states, on a square grid and on a ragged one (odd P,
 M not a multiple of the 64-point tile); the same for the certifying tendency of the PCG solver."""

@@ -11,9 +11,12 @@ OUT=$(mktemp -d); trap 'rm -rf "$OUT"' EXIT
 mkdir -p $PKG/lib/exp
 export HIPCC=$ROCM/bin/hipcc OUT SRC
 export FLAGS="-O3 -fPIC -std=c++17 --offload-arch=gfx950 -I$ROOT/include -I$SRC -Wall -Wno-unused-function $*"
+# the Makefile's NOFMA list: the files compiled with -ffp-contract=off
+export NOFMA=" $(sed -n 's/^NOFMA *= *//p' $PKG/Makefile) "
+[ "$NOFMA" != "  " ] || { echo "no NOFMA list in $PKG/Makefile" >&2; exit 1; }
 ls $SRC/*.hip | xargs -P 16 -I{} bash -c '
   f=$(basename {} .hip); X=""
-  case $f in qg_stencil|qg_ens_stats) X="-ffp-contract=off";; esac
+  case "$NOFMA" in *" $f "*) X="-ffp-contract=off";; esac
   $HIPCC $FLAGS $X -c {} -o $OUT/$f.o'
 $HIPCC --offload-arch=gfx950 -shared -o $PKG/lib/exp/$NAME.so $OUT/*.o -L$ROCM/lib -lrccl -Wl,-rpath,$ROCM/lib
 ls -la $PKG/lib/exp/$NAME.so

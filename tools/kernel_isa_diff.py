@@ -7,7 +7,7 @@ file before and after to gfx950 assembly and compare each function's instruction
     git show REV:julia-ocean-modelling_amd/csrc/qg_spectral.hip > /tmp/old/qg_spectral.hip   # and its headers
     hipcc $F -I/tmp/old /tmp/old/qg_spectral.hip -o old.s
     hipcc $F -Ijulia-ocean-modelling_amd/csrc julia-ocean-modelling_amd/csrc/qg_spectral.hip -o new.s
-    python tools/kernel_isa_diff.py old.s new.s        # (qg_stencil.hip: add -ffp-contract=off)
+    python tools/kernel_isa_diff.py old.s new.s        # (the Makefile's NOFMA files: add -ffp-contract=off)
 
 A file split into several (or several files against their parent's one): compile each to its
 own .s, concatenate them, and compare with the single old.s; the function labels summed over
@@ -47,7 +47,12 @@ qg_floats.hip (profiles/floats/isa_diff.txt).  Moving the record families' entry
 kernels (csrc/qg_owner.hpp, host code only) left every function of the seven files it touched
 identical, differing or missing 0, new only 0, the labels equal: qg_spectra.hip 20,
 qg_spectra2d.hip 28, qg_profiles.hip 12, qg_ens_stats.hip 4, qg_tracer.hip 7, qg_floats.hip 4,
-qg_diag.hip 3 (78 in all).
+qg_diag.hip 3 (78 in all).  The split of qg_stencil.hip into one file per tendency form (qg_ops.hip
+7, qg_tend_ring.hip 9, qg_tend_pair.hip 1, qg_tend_direct.hip 5, qg_tend_launch.hip 0 functions) left
+all 22 identical, differing or missing 0, new only 0, and qg_tracer.hip's 7 identical with the
+shared arakawa_point (profiles/tend_split/isa_diff.txt); the ring and pair kernels written without
+their prefetch-depth parameter (only PF = 1 exists) differed in all ten (tendency_kernel<256, 1,
+double> 4527 -> 4546 instructions, tendency_pair_kernel 7516 -> 7576), so the parameter stays.
 """
 import re
 import sys
