@@ -392,6 +392,46 @@ typedef struct qg_tend_plan {
 } qg_tend_plan;
 int qg_tendency_plan(int64_t M, const int rows[4], int esize, int cert, int nmembers, int resident,
                      int64_t cap, qg_tend_plan *out);
+/* The history slots one call reads, writes and moves, as the library decides them: for each of
+ * the four modes of qg_set_keep_order (rotating, store_new_state!'s order of model.jl:102-106, and
+ * the two SLOT1 modes), with or without a transport, Euler or AB3.  Pure host function (no device
+ * needed; a test applies the plans to labelled slots for every call order); the library's own
+ * calls go through the same planner.  Not part of the drop-in surface.
+ * The state is what the decision depends on: the heads (physical slot of logical slot 1 of zeta,
+ * psi, f_store), the keep-order mode, whether a transport is attached, whether a deferred move of
+ * the new zeta from slot 2 into slot 1 is pending, and whether the solver's first pass can carry
+ * that move (the spectral solver, power-of-two M >= 8).
+ * The plan, in the order a call carries it out: settle (the pending move completes first), move
+ * (canonicalize: row w = the source slot of each new slot of array w, -1 = the array stays),
+ * shift (store_new_state!'s slot 3 <- 2 <- 1 of zeta, psi, f_store before the launch), the
+ * physical slots the launch reads and writes (-1: none), fshift (the AB3 tendency rewrites
+ * F(t-1) and F(t-2) into these slots itself after reading them; -1: off), zeta_copy (the solve's
+ * first pass also stores the zeta it reads into this slot; -1: no), after (QG_SLOT_AFTER_*), and
+ * the state the call leaves.  timestep (1-based) matters to QG_SLOT_CALL_TENDENCY only.        */
+enum { QG_SLOT_CALL_TENDENCY = 0, QG_SLOT_CALL_SOLVE = 1, QG_SLOT_CALL_SETTLE = 2, QG_SLOT_CALL_CANONICALIZE = 3 };
+enum { QG_SLOT_AFTER_NONE = 0,  /* nothing                                                      */
+       QG_SLOT_AFTER_MOVE = 1,  /* zeta: slot 1 <- slot 2 now                                   */
+       QG_SLOT_AFTER_DEFER = 2  /* the same move left pending (the next state says so)          */ };
+typedef struct qg_slot_state {
+    int32_t heads[3];
+    int32_t keep_order;     /* 0, 1, QG_KEEP_ORDER_SLOT1, QG_KEEP_ORDER_SLOT1_DEFERRED          */
+    int32_t distributed;
+    int32_t zcopy_pending;
+    int32_t can_defer;
+    int32_t reserved;
+} qg_slot_state;
+typedef struct qg_slot_call {
+    int32_t settle;
+    int32_t move[3][3];
+    int32_t shift[3];
+    int32_t zeta_in, psi_in, f1_in, f2_in; /* read: zeta, psi, F(t-1), F(t-2)                   */
+    int32_t zeta_out, psi_out, f_out;      /* written                                           */
+    int32_t fshift[2];
+    int32_t zeta_copy;
+    int32_t after;
+    qg_slot_state next;
+} qg_slot_call;
+int qg_slot_plan(const qg_slot_state *state, int kind, int64_t timestep, qg_slot_call *out);
 
 /* ---- stateless kernels on (M+2, P+2) device fields (ghost ring refreshed on output) ---- */
 int qg_laplace_5p(const double *u, double *out, int64_t M, int64_t P, double dx, void *stream); /* laplacian.jl:15-27 */

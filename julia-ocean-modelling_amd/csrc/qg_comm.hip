@@ -16,7 +16,7 @@
 #include <thread>
 #include <vector>
 
-#include "qg_common.hpp"
+#include "qg_comm.hpp"
 
 namespace qg {
 

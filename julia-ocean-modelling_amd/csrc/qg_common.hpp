@@ -31,14 +31,8 @@ namespace qg {
 
 constexpr int WAVE = 64;
 
-// Bounded host wait on a stream (ev == nullptr) or an event, for a context with a transport
-// attached (comm != nullptr; qg_comm.hip): fails with QG_ERR_RCCL on an RCCL async error or
-// when no halo exchange completes within the transport's timeout.  comm == nullptr: a plain
-// hipStreamSynchronize / hipEventSynchronize.
-int comm_wait(void *comm, hipStream_t s, hipEvent_t ev, const char *what);
 // qg_set_form's value for `which` (QG_FORM_*; 0 = the automatic choice)
 int form(int which);
-int comm_set_timeout(void *comm, double seconds);
 // the parameter checks of qg_create (qg_capi.hip): host only, before any device call
 int check_create_params(const qg_params *p);
 

@@ -29,6 +29,7 @@
 #include "qg_mi355_ensemble.h"
 #include "qg_mi355_sweep.h"
 #include "qg_owner.hpp"
+#include "qg_slots.hpp"
 #include "qg_spectral.hpp"
 
 using namespace qg;
@@ -54,6 +55,11 @@ struct qg_ens {
 
     size_t member_stride() const { return 6 * F; }  // doubles between two members' blocks
     double *field(double *base, int layer, int slot) const { return base + F * (size_t)(layer + 2 * slot); }
+    // the slot planner's state (qg_slots.hpp): rotating, one rank, nothing deferred
+    qg_slot_state slot_state() const { return qg_slot_state{{heads[0], heads[1], heads[2]}, 0, 0, 0, 0, 0}; }
+    void store_slots(const qg_slot_state &s) {
+        for (int w = 0; w < 3; ++w) heads[w] = s.heads[w];
+    }
 };
 
 // the owner's side of the record families (qg_owner.hpp): host only
@@ -277,35 +283,36 @@ int qg_ens_initialise(qg_ens *e, const uint64_t *seed1, const uint64_t *seed2) {
 // evolve_zeta! of every member (rotating slots: the new values go to the oldest slot)
 static int ens_evolve_zeta(qg_ens *e, int64_t timestep) {
     const qg_params &p = e->p;
-    const int zh = e->heads[0], ph = e->heads[1], fh = e->heads[2], fh2 = (fh + 1) % 3;
-    const int zn = (zh + 2) % 3, fn = (fh + 2) % 3;
+    qg_slot_call pl;
+    plan_tendency(e->slot_state(), timestep, pl);
     // member 0's (visc, U, r): every member's, unless e->rec carries their own
     TendArgs a = tend_model_args<double>(p, e->mp[0].visc, e->mp[0].U, e->mp[0].r, e->d.beta1, e->d.beta2, timestep);
     a.write_ghost_rows = 1;
     a.wind = e->wind;
     for (int l = 0; l < 2; ++l) {
-        a.zeta[l] = e->field(e->zeta, l, zh);
-        a.psi[l] = e->field(e->psi, l, ph);
-        a.fprev1[l] = e->field(e->fst, l, fh);
-        a.fprev2[l] = e->field(e->fst, l, fh2);
-        a.zeta_out[l] = e->field(e->zeta, l, zn);
-        a.f_out[l] = e->field(e->fst, l, fn);
+        a.zeta[l] = e->field(e->zeta, l, pl.zeta_in);
+        a.psi[l] = e->field(e->psi, l, pl.psi_in);
+        a.fprev1[l] = e->field(e->fst, l, pl.f1_in);
+        a.fprev2[l] = e->field(e->fst, l, pl.f2_in);
+        a.zeta_out[l] = e->field(e->zeta, l, pl.zeta_out);
+        a.f_out[l] = e->field(e->fst, l, pl.f_out);
     }
     tend_wrap_rows(a);
     if (e->rec) QG_CHECK(launch_tendency_sweep(a, e->nmembers, (int64_t)e->member_stride(), e->rec, e->stream));
     else QG_CHECK(launch_tendency_members(a, e->nmembers, (int64_t)e->member_stride(), e->stream));
-    e->heads[0] = zn;
-    e->heads[2] = fn;
+    e->store_slots(pl.next);
     return QG_OK;
 }
 
 // evolve_psi! of every member
 static int ens_evolve_psi(qg_ens *e) {
-    const int zh = e->heads[0], pn = (e->heads[1] + 2) % 3;
+    qg_slot_call pl;
+    plan_solve(e->slot_state(), pl);
+    const int zh = pl.zeta_in, pn = pl.psi_out;
     QG_CHECK(e->spec.solve_members(e->field(e->zeta, 0, zh), e->field(e->zeta, 1, zh), e->field(e->psi, 0, pn),
                                    e->field(e->psi, 1, pn), (int64_t)(sizeof(double) * e->member_stride()),
                                    e->stream));
-    e->heads[1] = pn;
+    e->store_slots(pl.next);
     return QG_OK;
 }
 
@@ -326,7 +333,7 @@ int qg_ens_run(qg_ens *e, int64_t first_step, int64_t nsteps) {
 
 int qg_ens_slot(const qg_ens *e, int which, int logical, int *physical) {
     if (!e || !physical || which < 0 || which > 2 || logical < 1 || logical > 3) return QG_ERR_INVALID_ARG;
-    *physical = (e->heads[which] + logical - 1) % 3;
+    *physical = slot_of(e->heads[which], logical);
     return QG_OK;
 }
 
@@ -335,13 +342,8 @@ int qg_ens_canonicalize(qg_ens *e) {
     if (!e->zeta) return QG_ERR_NOT_BOUND;
     QG_HIP(hipSetDevice(e->device));
     // per member, one launch rotates every field whose newest slot is not physical 0 (qg_canonicalize)
-    int src[3][3], which[3], n = 0;
-    for (int w = 0; w < 3; ++w) {
-        if (e->heads[w] == 0) continue;
-        which[n] = w;
-        for (int q = 0; q < 3; ++q) src[n][q] = (e->heads[w] + q) % 3;
-        ++n;
-    }
+    int src[3][3], which[3];
+    const int n = canonical_moves(e->heads, 3, which, src);
     double *bases[3] = {e->zeta, e->psi, e->fst};
     for (int b = 0; n && b < e->nmembers; ++b) {
         void *arr[3];

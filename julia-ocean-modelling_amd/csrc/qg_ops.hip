@@ -1,5 +1,5 @@
 // Stand-alone stencil operators for gfx950 -- laplace_5p / cd / J / ghost fill -- the in-place
-// slot moves and the seeded initialisation, with their launchers.
+// slot moves and the seeded initialisation, with their launchers and the operators' C-ABI entries.
 //
 // Arithmetic follows the reference term by term and this file is compiled with
 // -ffp-contract=off, so results are bit-identical to oracle/qg_oracle.c:
@@ -217,3 +217,31 @@ int launch_initialise_global(void *zeta, void *psi, void *f_store, int esize, in
     return QG_OK;
 }
 }  // namespace qg
+
+using namespace qg;
+
+// ---- the C-ABI entries of the stateless operators (include/qg_mi355.h) ------------------------
+extern "C" {
+
+int qg_laplace_5p(const double *u, double *out, int64_t M, int64_t P, double dx, void *stream) {
+    if (!u || !out || M < 1 || P < 1 || !(dx > 0)) return QG_ERR_INVALID_ARG;
+    return launch_laplace(u, out, M, P, dx, static_cast<hipStream_t>(stream));
+}
+
+int qg_cd(const double *u, double *out, int64_t M, int64_t P, double dx, void *stream) {
+    if (!u || !out || M < 1 || P < 1 || !(dx > 0)) return QG_ERR_INVALID_ARG;
+    return launch_cd(u, out, M, P, dx, static_cast<hipStream_t>(stream));
+}
+
+int qg_arakawa_J(const double *zeta, const double *psi, double *out, int64_t M, int64_t P, double dx,
+                 void *stream) {
+    if (!zeta || !psi || !out || M < 1 || P < 1 || !(dx > 0)) return QG_ERR_INVALID_ARG;
+    return launch_arakawa(zeta, psi, out, M, P, dx, static_cast<hipStream_t>(stream));
+}
+
+int qg_fill_ghosts(double *b, int64_t M, int64_t P, void *stream) {
+    if (!b || M < 1 || P < 1) return QG_ERR_INVALID_ARG;
+    return launch_fill_ghosts(b, M, P, static_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"

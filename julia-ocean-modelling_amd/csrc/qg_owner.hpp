@@ -1,9 +1,9 @@
 // What the record families (spectra, 2-D spectra, profiles, ensemble statistics, tracers, floats)
 // need to know of their owner, a qg_ctx or a qg_ens: a host-side view of the newest state, filled
-// by qg_capi.hip for a qg_ctx and by qg_ensemble.hip for a qg_ens at every call (the newest slots
+// by qg_step.hip for a qg_ctx and by qg_ensemble.hip for a qg_ens at every call (the newest slots
 // move with every step), and the recorded-run loop all of them share.  The entry points of a
-// family live beside its kernels and are written once, for an Owner; qg_ctx and qg_ens stay
-// private to their files.
+// family live beside its kernels and are written once, for an Owner; qg_ctx (qg_ctx.hpp) and qg_ens stay
+// private to their own files.
 #pragma once
 
 #include "qg_common.hpp"
@@ -43,7 +43,7 @@ struct StateView {
     OwnerScratch *scratch = nullptr;
 };
 
-void view(qg_ctx *c, StateView *v);  // qg_capi.hip
+void view(qg_ctx *c, StateView *v);  // qg_step.hip
 void view(qg_ens *e, StateView *v);  // qg_ensemble.hip
 
 // the owner of a call: one of the two

@@ -16,6 +16,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "qg_comm.hpp"
 #include "qg_pcg.hpp"
 
 namespace qg {

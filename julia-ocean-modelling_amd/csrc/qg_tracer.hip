@@ -29,6 +29,7 @@
 #include <new>
 
 #include "qg_owner.hpp"
+#include "qg_slots.hpp"
 #include "qg_tend_dev.hpp"
 
 namespace qg {
@@ -441,11 +442,11 @@ static int tracers_advance(qg_tracers *t, const StateView &o) {
     a.U = o.U;
     a.psi[0] = f64(o.psi[0]);
     a.psi[1] = f64(o.psi[1]);
-    const int ch = t->heads[0], gh = t->heads[1], cn = (ch + 2) % 3, gn = (gh + 2) % 3;
+    const int ch = t->heads[0], gh = t->heads[1], cn = slot_oldest(ch), gn = slot_oldest(gh);
     a.c_in = t->c + t->slot_off(o, ch);
     a.c_out = t->c + t->slot_off(o, cn);
     a.g1 = t->g + t->slot_off(o, gh);
-    a.g2 = t->g + t->slot_off(o, (gh + 1) % 3);
+    a.g2 = t->g + t->slot_off(o, slot_of(gh, 2));
     a.g_out = t->g + t->slot_off(o, gn);
     for (int k = 0; k < t->nt; ++k) {
         const int l = t->tp[k].layer;
@@ -556,7 +557,7 @@ int qg_tracers_diagnostics(qg_tracers *t, double *out) {
 
 int qg_tracers_slot(const qg_tracers *t, int which, int logical, int *physical) {
     if (!t || !physical || which < 0 || which > 1 || logical < 1 || logical > 3) return QG_ERR_INVALID_ARG;
-    *physical = (t->heads[which] + logical - 1) % 3;
+    *physical = slot_of(t->heads[which], logical);
     return QG_OK;
 }
 

@@ -41,6 +41,8 @@ QG_KEEP_ORDER_SLOT1, QG_KEEP_ORDER_SLOT1_DEFERRED = 2, 3
 QG_FORM_TENDENCY, QG_FORM_TENDENCY_TILE, QG_FORM_ROW_SPLIT, QG_FORM_PCG_NO_CERTIFICATE = 0, 1, 2, 3
 QG_TEND_AUTO, QG_TEND_RING, QG_TEND_DIRECT, QG_TEND_ONE_POINT = 0, 1, 2, 3
 QG_TEND_KERNEL_RING, QG_TEND_KERNEL_PAIR, QG_TEND_KERNEL_DIRECT = 0, 1, 2
+QG_SLOT_CALL_TENDENCY, QG_SLOT_CALL_SOLVE, QG_SLOT_CALL_SETTLE, QG_SLOT_CALL_CANONICALIZE = 0, 1, 2, 3
+QG_SLOT_AFTER_NONE, QG_SLOT_AFTER_MOVE, QG_SLOT_AFTER_DEFER = 0, 1, 2
 
 
 class QgParams(C.Structure):
@@ -97,6 +99,23 @@ class QgTendPlan(C.Structure):
     _fields_ = [("kernel", C.c_int32), ("width", C.c_int32), ("threads", C.c_int32), ("rows", C.c_int32),
                 ("chipfulls", C.c_int32), ("nx", C.c_int32), ("nyA", C.c_int32), ("nyB", C.c_int32),
                 ("nz", C.c_int32), ("reserved", C.c_int32), ("blocks", C.c_int64)]
+
+
+class QgSlotState(C.Structure):
+    """Mirror of ``struct qg_slot_state``: what qg_slot_plan decides from."""
+
+    _fields_ = [("heads", C.c_int32 * 3), ("keep_order", C.c_int32), ("distributed", C.c_int32),
+                ("zcopy_pending", C.c_int32), ("can_defer", C.c_int32), ("reserved", C.c_int32)]
+
+
+class QgSlotCall(C.Structure):
+    """Mirror of ``struct qg_slot_call``: qg_slot_plan's plan of one call."""
+
+    _fields_ = [("settle", C.c_int32), ("move", (C.c_int32 * 3) * 3), ("shift", C.c_int32 * 3),
+                ("zeta_in", C.c_int32), ("psi_in", C.c_int32), ("f1_in", C.c_int32), ("f2_in", C.c_int32),
+                ("zeta_out", C.c_int32), ("psi_out", C.c_int32), ("f_out", C.c_int32),
+                ("fshift", C.c_int32 * 2), ("zeta_copy", C.c_int32), ("after", C.c_int32),
+                ("next", QgSlotState)]
 
 
 class QgStats(C.Structure):
@@ -156,6 +175,7 @@ SIGNATURES = [
     ("qg_get_form", C.c_int, [C.c_int]),
     ("qg_tendency_plan", C.c_int, [_i64, C.c_int * 4, C.c_int, C.c_int, C.c_int, C.c_int, _i64,
                                    C.POINTER(QgTendPlan)]),
+    ("qg_slot_plan", C.c_int, [C.POINTER(QgSlotState), C.c_int, _i64, C.POINTER(QgSlotCall)]),
     ("qg_laplace_5p", C.c_int, [_dp, _dp, _i64, _i64, C.c_double, _vp]),
     ("qg_cd", C.c_int, [_dp, _dp, _i64, _i64, C.c_double, _vp]),
     ("qg_arakawa_J", C.c_int, [_dp, _dp, _dp, _i64, _i64, C.c_double, _vp]),

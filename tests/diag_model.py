@@ -337,7 +337,7 @@ def device_order(zeta, psi, dx, mutant=None):
 
 
 def rank_fold(records):
-    """qg_diagnostics' host fold over the ranks' records, in rank order (csrc/qg_capi.hip)."""
+    """qg_diagnostics' host fold over the ranks' records, in rank order (csrc/qg_ctx_io.hip)."""
     v = np.array(records[0], dtype=np.float64)
     with np.errstate(invalid="ignore", over="ignore"):
         for q in records[1:]:

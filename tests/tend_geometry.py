@@ -27,7 +27,7 @@ need target >= 9 for the certifying kernel at (200, 37) (nx = 2: 6 resident work
 chip) and >= 3 elsewhere (nx <= 5, waves = 2: 15 resident workgroups), far below any CDNA
 part; min_target() returns the figures and the CPU test pins them.
 
-Slabs (csrc/qg_capi.hip, evolve_zeta_t): with the halo overlap on and P_local >= 8 a step is
+Slabs (csrc/qg_step.hip, evolve_zeta_t): with the halo overlap on and P_local >= 8 a step is
 two launches, the interior rows [2, P_local - 2) and then the two row ranges [0, 2) +
 [P_local - 2, P_local) in one grid (the kernels' `second` branch); otherwise one launch of all
 rows.  Rows outside [0, P_local) come from received halo rows, so only range-checked bodies

@@ -53,6 +53,10 @@ all 22 identical, differing or missing 0, new only 0, and qg_tracer.hip's 7 iden
 shared arakawa_point (profiles/tend_split/isa_diff.txt); the ring and pair kernels written without
 their prefetch-depth parameter (only PF = 1 exists) differed in all ten (tendency_kernel<256, 1,
 double> 4527 -> 4546 instructions, tendency_pair_kernel 7516 -> 7576), so the parameter stays.
+The split of qg_capi.hip by concern (qg_capi, qg_step, qg_ctx_io, qg_ctx_comm, qg_solver: host code,
+0 functions each) with the operator entries moved into qg_ops.hip and the slot planner (qg_slots.hpp)
+left qg_ops.hip 7, qg_tracer.hip 7, qg_comm.hip 5 and qg_pcg.hip 22 identical, differing or missing
+0, new only 0, the labels equal (profiles/ctx_split/isa_diff.txt).
 """
 import re
 import sys
