@@ -309,40 +309,18 @@ __global__ void pcg_mg_zpin(PcgArgs a) {
     a.scal[PCG_RSUM + 1] = 0.0;
 }
 
-// sum the per-block partials (fixed order) -> rank sums in scal[RSUM + 0/1]
-__global__ __launch_bounds__(1024) void pcg_rank_sum(PcgArgs a, int nblk) {
-    __shared__ double s0[1024], s1[1024];
-    double t0 = 0, t1 = 0;
-    for (int b = threadIdx.x; b < nblk; b += 1024) {
-        t0 += a.partial[2 * b];
-        t1 += a.partial[2 * b + 1];
-    }
-    s0[threadIdx.x] = t0;
-    s1[threadIdx.x] = t1;
-    __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) {
-        if (threadIdx.x < o) {
-            s0[threadIdx.x] += s0[threadIdx.x + o];
-            s1[threadIdx.x] += s1[threadIdx.x + o];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        a.scal[PCG_RSUM] = s0[0];
-        a.scal[PCG_RSUM + 1] = s1[0];
-    }
-}
-
-// sum NV per-block partials (fixed order) -> scal[PCG_RSUM6 ..)
+// The one reduction tree of a 1024-thread block over nblk per-block partials of NV values each,
+// in a fixed order per value: thread t adds partials t, t + 1024, ... in turn, then the 1024
+// sums are halved 512 -> 1 in LDS.  Every thread may read value k from sm[k][0] afterwards.
 template <int NV>
-__global__ __launch_bounds__(1024) void pcg_rank_sumN(PcgArgs a, int nblk) {
-    __shared__ double sm[NV][1024];
+__device__ __forceinline__ void partial_tree(const double *part, int nblk, double (&sm)[NV][1024]) {
     double t[NV];
 #pragma unroll
     for (int k = 0; k < NV; ++k) t[k] = 0;
-    for (int b = threadIdx.x; b < nblk; b += 1024)
+    for (int b = threadIdx.x; b < nblk; b += 1024) {
 #pragma unroll
-        for (int k = 0; k < NV; ++k) t[k] += a.partial[NV * b + k];
+        for (int k = 0; k < NV; ++k) t[k] += part[NV * (size_t)b + k];
+    }
 #pragma unroll
     for (int k = 0; k < NV; ++k) sm[k][threadIdx.x] = t[k];
     __syncthreads();
@@ -352,16 +330,29 @@ __global__ __launch_bounds__(1024) void pcg_rank_sumN(PcgArgs a, int nblk) {
             for (int k = 0; k < NV; ++k) sm[k][threadIdx.x] += sm[k][threadIdx.x + o];
         __syncthreads();
     }
+}
+
+// sum the per-block partials -> rank sums in scal[RSUM + 0/1]
+__global__ __launch_bounds__(1024) void pcg_rank_sum(PcgArgs a, int nblk) {
+    __shared__ double sm[2][1024];
+    partial_tree<2>(a.partial, nblk, sm);
+    if (threadIdx.x < 2) a.scal[PCG_RSUM + threadIdx.x] = sm[threadIdx.x][0];
+}
+
+// sum NV per-block partials -> scal[PCG_RSUM6 ..)
+template <int NV>
+__global__ __launch_bounds__(1024) void pcg_rank_sumN(PcgArgs a, int nblk) {
+    __shared__ double sm[NV][1024];
+    partial_tree<NV>(a.partial, nblk, sm);
     if (threadIdx.x < NV) a.scal[PCG_RSUM6 + threadIdx.x] = sm[threadIdx.x][0];
 }
 
-// fast-path scalars from the (gathered) sums: what 0: (b,z),(z,Bz),(b,b) -> alpha, rz, bb;
-// what 1: ||r1||^2 -> rr; what 2: (b,b), (r0,r0) -> bb, rr
+// the openings' scalars from their (gathered) sums of nv values per rank; what: PCG_F_*
 __global__ void pcg_fast_scalar(PcgArgs a, int what, const double *gathered, int nv, int nranks) {
     if (threadIdx.x != 0) return;
     for (int s = 0; s < 2; ++s) {
         double *sc = a.scal;
-        if (what == 0) {
+        if (what == PCG_F_ALPHA) {
             double bz = 0, zq = 0, bb = 0;
             for (int g = 0; g < nranks; ++g) {
                 bz += gathered[nv * g + 3 * s];
@@ -371,11 +362,11 @@ __global__ void pcg_fast_scalar(PcgArgs a, int what, const double *gathered, int
             sc[PCG_ALPHA + s] = (zq != 0 && bz != 0) ? bz / zq : 0.0;
             sc[PCG_RZ + s] = bz;
             sc[PCG_BB + s] = bb;
-        } else if (what == 1) {
+        } else if (what == PCG_F_RR) {
             double rr = 0;
             for (int g = 0; g < nranks; ++g) rr += gathered[nv * g + s];
             sc[PCG_RR + s] = rr;
-        } else {  // what 2: certified step, (b,b), (r0,r0) per system
+        } else {  // PCG_F_CERT
             double bb = 0, rr = 0;
             for (int g = 0; g < nranks; ++g) {
                 bb += gathered[nv * g + 2 * s];
@@ -387,28 +378,26 @@ __global__ void pcg_fast_scalar(PcgArgs a, int what, const double *gathered, int
     }
 }
 
-// combine the (gathered) rank sums and derive the next scalar
-//   what: 0 = ||b||^2, 1 = alpha = rz / pq, 2 = ||r||^2, 3 = beta = rz_new / rz (rz <- rz_new),
-//         4 = initial rz, 5 = sum of the Poisson residual, 6 = z at the pin
+// combine the (gathered) rank sums and derive the next scalar; what: PCG_S_*
 __global__ void pcg_scalar(PcgArgs a, int what, const double *gathered, int nranks) {
     if (threadIdx.x != 0) return;
-    if (what == 5 || what == 6) {  // multigrid: sum(r_Poisson), z_pin (system 0 only)
+    if (what == PCG_S_SUMR || what == PCG_S_ZPIN) {
         double v = 0;
         for (int g = 0; g < nranks; ++g) v += gathered[2 * g];
-        a.scal[what == 5 ? PCG_SUMR : PCG_ZPIN] = v;
+        a.scal[what == PCG_S_SUMR ? PCG_SUMR : PCG_ZPIN] = v;
         return;
     }
     for (int s = 0; s < 2; ++s) {
         double v = 0;
         for (int g = 0; g < nranks; ++g) v += gathered[2 * g + s];
         double *sc = a.scal;
-        if (what == 0) sc[PCG_BB + s] = v;
-        else if (what == 1) sc[PCG_ALPHA + s] = (v != 0 && sc[PCG_RZ + s] != 0) ? sc[PCG_RZ + s] / v : 0.0;
-        else if (what == 2) sc[PCG_RR + s] = v;
-        else if (what == 3) {
+        if (what == PCG_S_BB) sc[PCG_BB + s] = v;
+        else if (what == PCG_S_ALPHA) sc[PCG_ALPHA + s] = (v != 0 && sc[PCG_RZ + s] != 0) ? sc[PCG_RZ + s] / v : 0.0;
+        else if (what == PCG_S_RR) sc[PCG_RR + s] = v;
+        else if (what == PCG_S_BETA) {
             sc[PCG_BETA + s] = sc[PCG_RZ + s] != 0 ? v / sc[PCG_RZ + s] : 0.0;
             sc[PCG_RZ + s] = v;
-        } else if (what == 4) {  // initial rz
+        } else if (what == PCG_S_RZ0) {
             sc[PCG_RZ + s] = v;
         }
     }
@@ -434,30 +423,18 @@ __device__ void cert_latch(PcgArgs a, double *latch, double rtol, const double b
     latch[3] = (worst != worst || w != w) ? (worst + w) : (worst > w ? worst : w);
 }
 
-// from the check pass's scalars (pcg_fast_scalar what 2)
+// from the check pass's scalars (pcg_fast_scalar, PCG_F_CERT)
 __global__ void pcg_cert_latch_scal(PcgArgs a, double *latch, double rtol) {
     if (threadIdx.x != 0) return;
     const double bb[2] = {a.scal[PCG_BB], a.scal[PCG_BB + 1]}, rr[2] = {a.scal[PCG_RR], a.scal[PCG_RR + 1]};
     cert_latch(a, latch, rtol, bb, rr);
 }
 
-// from the certifying tendency's partials (fixed order)
+// from the certifying tendency's partials
 __global__ __launch_bounds__(1024) void pcg_cert_latch_part(PcgArgs a, const double *part, int nblk, double *latch,
                                                             double rtol) {
     __shared__ double sm[4][1024];
-    double t[4] = {0, 0, 0, 0};
-    for (int b = threadIdx.x; b < nblk; b += 1024)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) t[k] += part[4 * (size_t)b + k];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) sm[k][threadIdx.x] = t[k];
-    __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) {
-        if (threadIdx.x < o)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) sm[k][threadIdx.x] += sm[k][threadIdx.x + o];
-        __syncthreads();
-    }
+    partial_tree<4>(part, nblk, sm);
     if (threadIdx.x == 0) {
         const double bb[2] = {sm[0][0], sm[2][0]}, rr[2] = {sm[1][0], sm[3][0]};
         cert_latch(a, latch, rtol, bb, rr);
@@ -545,13 +522,19 @@ PcgSolver::~PcgSolver() {
     if (mem_) (void)hipFree(mem_);
 }
 
-int PcgSolver::reduce(int what, hipStream_t s, SpectralSolver::GatherFn gather, void *user) {
-    if (what != 6) {  // (6: the rank value is in scal[RSUM] already)
+// the launch grid of the point kernels (PCG_FOR_POINTS) for one solve's arguments
+static dim3 point_grid(const PcgArgs &a) {
+    return dim3((unsigned)((a.M + PCG_T - 1) / PCG_T), (unsigned)std::min<int64_t>(a.P, PCG_ROWB));
+}
+
+int PcgSolver::reduce(int what, const Via &v, bool summed) {
+    const hipStream_t s = v.s;
+    if (!summed) {
         pcg_rank_sum<<<1, 1024, 0, s>>>(a_, nblk_);
         QG_LAUNCH_CHECK();
     }
-    if (gather) {
-        QG_CHECK(gather(user, a_.scal + PCG_RSUM, gathered_, 2, s));
+    if (v.gather) {
+        QG_CHECK(v.gather(v.user, a_.scal + PCG_RSUM, gathered_, 2, s));
         pcg_scalar<<<1, 64, 0, s>>>(a_, what, gathered_, a_.nranks);
     } else {
         pcg_scalar<<<1, 64, 0, s>>>(a_, what, a_.scal + PCG_RSUM, 1);
@@ -561,29 +544,29 @@ int PcgSolver::reduce(int what, hipStream_t s, SpectralSolver::GatherFn gather, 
 }
 
 // z = T^T V T r (see pcg_mg_sum); the Helmholtz system (and an unpinned Poisson one) is V r
-int PcgSolver::mg_precond(hipStream_t s, SpectralSolver::GatherFn gather, void *user, HaloFn halo, void *halo_user) {
+int PcgSolver::mg_precond(const Via &v) {
     PcgArgs &a = a_;
-    const dim3 grid((unsigned)((a.M + PCG_T - 1) / PCG_T), (unsigned)std::min<int64_t>(a.P, PCG_ROWB));
+    const hipStream_t s = v.s;
     const bool pin = a.pinned0 != 0;
     if (pin) {
-        pcg_mg_sum<<<grid, PCG_T, 0, s>>>(a);
+        pcg_mg_sum<<<point_grid(a), PCG_T, 0, s>>>(a);
         QG_LAUNCH_CHECK();
-        QG_CHECK(reduce(5, s, gather, user));
+        QG_CHECK(reduce(PCG_S_SUMR, v));
         pcg_mg_pin_rhs<<<1, 64, 0, s>>>(a, 1);
         QG_LAUNCH_CHECK();
     }
-    QG_CHECK(mg_.apply(a.r[0], a.r[1], a.z[0], a.z[1], s, gather, user, halo, halo_user));
+    QG_CHECK(mg_.apply(a.r[0], a.r[1], a.z[0], a.z[1], s, v.gather, v.user, v.halo, v.halo_user));
     if (pin) {
         pcg_mg_pin_rhs<<<1, 64, 0, s>>>(a, 0);
         QG_LAUNCH_CHECK();
-        pcg_mg_zpin<<<1, 64, 0, s>>>(a);
+        pcg_mg_zpin<<<1, 64, 0, s>>>(a);  // (this rank's part, straight into scal[RSUM])
         QG_LAUNCH_CHECK();
-        QG_CHECK(reduce(6, s, gather, user));  // (z -= z_pin: in the pcg_dot_rz that follows)
+        QG_CHECK(reduce(PCG_S_ZPIN, v, true));  // (z -= z_pin: in the pcg_dot_rz that follows)
     }
     return QG_OK;
 }
 
-// fast-path reductions: NV partials per block -> rank sums -> (all-gather) -> scalars
+// the openings' reductions: NV partials per block -> rank sums -> (all-gather) -> scalars
 template <int NV>
 static int reduce_fast(PcgArgs &a, int nblk, int what, double *gathered, hipStream_t s,
                        SpectralSolver::GatherFn gather, void *user) {
@@ -621,10 +604,9 @@ int PcgSolver::latch_fused(int nblk, hipStream_t s) {
 int PcgSolver::certify_pending(hipStream_t s, SpectralSolver::GatherFn gather, void *user) {
     if (!pending_) return QG_OK;
     // prev_: the arguments (inputs, outputs) of the solve being certified
-    const dim3 grid((unsigned)((prev_.M + PCG_T - 1) / PCG_T), (unsigned)std::min<int64_t>(prev_.P, PCG_ROWB));
-    pcg_cert_check<<<grid, PCG_T, 0, s>>>(prev_);
+    pcg_cert_check<<<point_grid(prev_), PCG_T, 0, s>>>(prev_);
     QG_LAUNCH_CHECK();
-    QG_CHECK(reduce_fast<4>(prev_, nblk_, 2, gathered_, s, gather, user));
+    QG_CHECK(reduce_fast<4>(prev_, nblk_, PCG_F_CERT, gathered_, s, gather, user));
     pcg_cert_latch_scal<<<1, 64, 0, s>>>(prev_, latch_, rtol_);
     QG_LAUNCH_CHECK();
     pending_ = false;
@@ -636,6 +618,115 @@ int PcgSolver::reset_latch(hipStream_t s) {
     return QG_OK;
 }
 
+int PcgSolver::precondition(const Via &v) {
+    PcgArgs &a = a_;
+    if (precond_ == QG_PRECOND_SPECTRAL) {
+        QG_CHECK(pre_.solve(a.r[0], a.r[1], a.z[0], a.z[1], a.ghost_rows, v.s, v.gather, v.user));
+    } else if (precond_ == QG_PRECOND_MULTIGRID) {
+        QG_CHECK(mg_precond(v));
+    } else {
+        const size_t F = (size_t)(a.M + 2) * (size_t)(a.P + 2);
+        for (int k = 0; k < 2; ++k)
+            QG_HIP(hipMemcpyAsync(a.z[k], a.r[k], sizeof(double) * F, hipMemcpyDeviceToDevice, v.s));
+    }
+    return QG_OK;
+}
+
+int PcgSolver::refresh_ghost_rows(double *f0, double *f1, const Via &v) {
+    if (!a_.ghost_rows && v.halo) {
+        double *f[2] = {f0, f1};
+        QG_CHECK(v.halo(v.halo_user, f, 2, a_.M, a_.P, -1, nullptr, v.s));
+    }
+    return QG_OK;
+}
+
+int PcgSolver::spectral_from_input(double *o1, double *o2, const double *proj_out, const Via &v) {
+    const PcgArgs &a = a_;
+    QG_CHECK(pre_.solve(a.in1, a.in2, o1, o2, a.ghost_rows, v.s, v.gather, v.user, a.proj_in, proj_out));
+    return refresh_ghost_rows(o1, o2, v);
+}
+
+int PcgSolver::next_direction(bool first, const Via &v) {
+    PcgArgs &a = a_;
+    const hipStream_t s = v.s;
+    // the multigrid form's T^T step rides on the pcg_dot_rz after each preconditioner call
+    const int unpin = precond_ == QG_PRECOND_MULTIGRID && a.pinned0 ? 1 : 0;
+    QG_CHECK(precondition(v));
+    pcg_dot_rz<<<point_grid(a), PCG_T, 0, s>>>(a, unpin);
+    QG_LAUNCH_CHECK();
+    QG_CHECK(reduce(first ? PCG_S_RZ0 : PCG_S_BETA, v));
+    pcg_pupdate<<<point_grid(a), PCG_T, 0, s>>>(a, first ? 1 : 0);
+    QG_LAUNCH_CHECK();
+    return refresh_ghost_rows(a.p[0], a.p[1], v);
+}
+
+int PcgSolver::read_residual(int it, const Via &v, bool *done) {
+    double host[PCG_NSCAL];
+    QG_HIP(hipMemcpyAsync(host, a_.scal, sizeof(host), hipMemcpyDeviceToHost, v.s));
+    QG_CHECK(comm_wait(v.user, v.s, nullptr, "PCG residual read"));
+    iters_ = it;
+    *done = true;
+    for (int k = 0; k < 2; ++k) {
+        const double bb = host[PCG_BB + k], rr = host[PCG_RR + k];
+        relres_[k] = bb > 0 ? std::sqrt(rr / bb) : std::sqrt(rr);
+        if (!(relres_[k] <= rtol_)) *done = false;
+    }
+    return QG_OK;
+}
+
+// psi = P_fwd z0 straight from the spectral solve, then one certification pass; if that fails,
+// the restart state (x0 = z0, r0 = b - B z0; bb already set) and its first direction
+int PcgSolver::open_certified(const Via &v, int *start) {
+    PcgArgs &a = a_;
+    const hipStream_t s = v.s;
+    QG_CHECK(spectral_from_input(a.out1, a.out2, a.proj_out, v));
+    pcg_cert_check<<<point_grid(a), PCG_T, 0, s>>>(a);
+    QG_LAUNCH_CHECK();
+    QG_CHECK(reduce_fast<4>(a, nblk_, PCG_F_CERT, gathered_, s, v.gather, v.user));
+    bool done;
+    QG_CHECK(read_residual(1, v, &done));
+    *start = done ? CONVERGED : 2;
+    if (done) return QG_OK;  // psi is the certified z0
+    pcg_cert_restart<<<point_grid(a), PCG_T, 0, s>>>(a);
+    QG_LAUNCH_CHECK();
+    return next_direction(true, v);
+}
+
+// z0 = B^-1 b straight from zeta: B^-1 (-proj_in zeta) = A^-1 proj_in zeta, i.e. the spectral
+// solve with the model's projection (the pin row of b is irrelevant to it); then iteration 1
+// fused (pcg_fast_dots, pcg_fast_finish).  If that misses the target, the general loop's state
+// after iteration 1 and the tail of that iteration: z1 = M^-1 r1, beta, p1 = z1 + beta p0.
+int PcgSolver::open_alpha(const Via &v, int *start) {
+    PcgArgs &a = a_;
+    const hipStream_t s = v.s;
+    const double id[4] = {1, 0, 0, 1};
+    QG_CHECK(spectral_from_input(a.z[0], a.z[1], id, v));
+    pcg_fast_dots<<<point_grid(a), PCG_T, 0, s>>>(a);
+    QG_LAUNCH_CHECK();
+    QG_CHECK(reduce_fast<6>(a, nblk_, PCG_F_ALPHA, gathered_, s, v.gather, v.user));
+    pcg_fast_finish<<<point_grid(a), PCG_T, 0, s>>>(a);
+    QG_LAUNCH_CHECK();
+    QG_CHECK(reduce_fast<2>(a, nblk_, PCG_F_RR, gathered_, s, v.gather, v.user));
+    bool done;
+    QG_CHECK(read_residual(1, v, &done));
+    *start = done ? CONVERGED : 2;
+    if (done) return QG_OK;  // psi already written by pcg_fast_finish
+    pcg_fast_materialize<<<point_grid(a), PCG_T, 0, s>>>(a);
+    QG_LAUNCH_CHECK();
+    QG_CHECK(refresh_ghost_rows(a.p[0], a.p[1], v));
+    // (a direction is for the iteration that uses it: none when the loop will not run)
+    return *start <= maxit_ ? next_direction(false, v) : QG_OK;
+}
+
+// from x0 = 0: b = r0 from zeta, ||b||^2 and the first direction
+int PcgSolver::open_general(const Via &v, int *start) {
+    pcg_rhs<<<point_grid(a_), PCG_T, 0, v.s>>>(a_);
+    QG_LAUNCH_CHECK();
+    QG_CHECK(reduce(PCG_S_BB, v));
+    *start = 1;
+    return next_direction(true, v);
+}
+
 int PcgSolver::solve(const double *in1, const double *in2, double *out1, double *out2, int ghost_rows,
                      hipStream_t s, SpectralSolver::GatherFn gather, void *user, HaloFn halo, void *halo_user) {
     if (!mem_) return QG_ERR_NOT_BOUND;
@@ -645,121 +736,26 @@ int PcgSolver::solve(const double *in1, const double *in2, double *out1, double 
     a.out1 = out1;
     a.out2 = out2;
     a.ghost_rows = ghost_rows;
-    const dim3 grid((unsigned)((a.M + PCG_T - 1) / PCG_T), (unsigned)std::min<int64_t>(a.P, PCG_ROWB));
-    auto precond = [&]() -> int {
-        if (precond_ == QG_PRECOND_SPECTRAL) {
-            QG_CHECK(pre_.solve(a.r[0], a.r[1], a.z[0], a.z[1], ghost_rows, s, gather, user));
-        } else if (precond_ == QG_PRECOND_MULTIGRID) {
-            QG_CHECK(mg_precond(s, gather, user, halo, halo_user));
-        } else {
-            const size_t F = (size_t)(a.M + 2) * (size_t)(a.P + 2);
-            for (int k = 0; k < 2; ++k)
-                QG_HIP(hipMemcpyAsync(a.z[k], a.r[k], sizeof(double) * F, hipMemcpyDeviceToDevice, s));
-        }
-        return QG_OK;
-    };
-    auto fix_p_ghosts = [&]() -> int {
-        if (!ghost_rows && halo) {
-            double *f[2] = {a.p[0], a.p[1]};
-            QG_CHECK(halo(halo_user, f, 2, a.M, a.P, -1, nullptr, s));
-        }
-        return QG_OK;
-    };
-    // the multigrid form's T^T step rides on the pcg_dot_rz after each preconditioner call
-    const int unpin = precond_ == QG_PRECOND_MULTIGRID && a.pinned0 ? 1 : 0;
-    double host[PCG_NSCAL];
+    const Via v{s, gather, user, halo, halo_user};
     iters_ = 0;
     relres_[0] = relres_[1] = -1;
-    int status = QG_ERR_NOT_CONVERGED;
-    bool resume = false;  // continue the general loop after a fast first iteration
-    int first_it = 1;
     if (deferred() && out2) {
         // deferred: the spectral solve, then the check on the device -- in the next tendency
         // (fuse_) or right here -- with the verdict latched (latch_); no host round trip
         // a previous solve's fused check that never got its tendency runs first
         QG_CHECK(certify_pending(s, gather, user));
-        QG_CHECK(pre_.solve(a.in1, a.in2, a.out1, a.out2, ghost_rows, s, gather, user, a.proj_in, a.proj_out));
-        if (!ghost_rows && halo) {
-            double *f[2] = {a.out1, a.out2};
-            QG_CHECK(halo(halo_user, f, 2, a.M, a.P, -1, nullptr, s));
-        }
+        QG_CHECK(spectral_from_input(a.out1, a.out2, a.proj_out, v));
         iters_ = 1;
         prev_ = a;
         pending_ = true;
         if (!fuse_) QG_CHECK(certify_pending(s, gather, user));
         return QG_OK;
     }
-    if (precond_ == QG_PRECOND_SPECTRAL && cert_ && out2) {
-        // psi = P_fwd z0 straight from the spectral solve, then one certification pass
-        QG_CHECK(pre_.solve(a.in1, a.in2, a.out1, a.out2, ghost_rows, s, gather, user, a.proj_in, a.proj_out));
-        if (!ghost_rows && halo) {
-            double *f[2] = {a.out1, a.out2};
-            QG_CHECK(halo(halo_user, f, 2, a.M, a.P, -1, nullptr, s));
-        }
-        pcg_cert_check<<<grid, PCG_T, 0, s>>>(a);
-        QG_LAUNCH_CHECK();
-        QG_CHECK(reduce_fast<4>(a, nblk_, 2, gathered_, s, gather, user));
-        QG_HIP(hipMemcpyAsync(host, a.scal, sizeof(host), hipMemcpyDeviceToHost, s));
-        QG_CHECK(comm_wait(user, s, nullptr, "PCG residual read"));
-        iters_ = 1;
-        bool done = true;
-        for (int k = 0; k < 2; ++k) {
-            const double bb = host[PCG_BB + k], rr = host[PCG_RR + k];
-            relres_[k] = bb > 0 ? std::sqrt(rr / bb) : std::sqrt(rr);
-            if (!(relres_[k] <= rtol_)) done = false;
-        }
-        if (done) return QG_OK;  // psi is the certified z0
-        pcg_cert_restart<<<grid, PCG_T, 0, s>>>(a);  // x0 = z0, r0 = b - B z0; bb already set
-        QG_LAUNCH_CHECK();
-        QG_CHECK(precond());
-        pcg_dot_rz<<<grid, PCG_T, 0, s>>>(a, unpin);
-        QG_LAUNCH_CHECK();
-        QG_CHECK(reduce(4, s, gather, user));
-        pcg_pupdate<<<grid, PCG_T, 0, s>>>(a, 1);
-        QG_LAUNCH_CHECK();
-        QG_CHECK(fix_p_ghosts());
-        first_it = 2;
-    } else if (precond_ == QG_PRECOND_SPECTRAL) {
-        // z0 = B^-1 b straight from zeta: B^-1 (-proj_in zeta) = A^-1 proj_in zeta, i.e. the
-        // spectral solve with the model's projection (the pin row of b is irrelevant to it)
-        const double id[4] = {1, 0, 0, 1};
-        QG_CHECK(pre_.solve(a.in1, a.in2, a.z[0], a.z[1], ghost_rows, s, gather, user, a.proj_in, id));
-        if (!ghost_rows && halo) {
-            double *f[2] = {a.z[0], a.z[1]};
-            QG_CHECK(halo(halo_user, f, 2, a.M, a.P, -1, nullptr, s));
-        }
-        pcg_fast_dots<<<grid, PCG_T, 0, s>>>(a);
-        QG_LAUNCH_CHECK();
-        QG_CHECK(reduce_fast<6>(a, nblk_, 0, gathered_, s, gather, user));
-        pcg_fast_finish<<<grid, PCG_T, 0, s>>>(a);
-        QG_LAUNCH_CHECK();
-        QG_CHECK(reduce_fast<2>(a, nblk_, 1, gathered_, s, gather, user));
-        QG_HIP(hipMemcpyAsync(host, a.scal, sizeof(host), hipMemcpyDeviceToHost, s));
-        QG_CHECK(comm_wait(user, s, nullptr, "PCG residual read"));
-        iters_ = 1;
-        bool done = true;
-        for (int k = 0; k < 2; ++k) {
-            const double bb = host[PCG_BB + k], rr = host[PCG_RR + k];
-            relres_[k] = bb > 0 ? std::sqrt(rr / bb) : std::sqrt(rr);
-            if (!(relres_[k] <= rtol_)) done = false;
-        }
-        if (done) return QG_OK;  // psi already written by pcg_fast_finish
-        pcg_fast_materialize<<<grid, PCG_T, 0, s>>>(a);
-        QG_LAUNCH_CHECK();
-        QG_CHECK(fix_p_ghosts());
-        resume = true;
-    } else {
-        pcg_rhs<<<grid, PCG_T, 0, s>>>(a);
-        QG_LAUNCH_CHECK();
-        QG_CHECK(reduce(0, s, gather, user));
-        QG_CHECK(precond());
-        pcg_dot_rz<<<grid, PCG_T, 0, s>>>(a, unpin);
-        QG_LAUNCH_CHECK();
-        QG_CHECK(reduce(4, s, gather, user));
-        pcg_pupdate<<<grid, PCG_T, 0, s>>>(a, 1);
-        QG_LAUNCH_CHECK();
-        QG_CHECK(fix_p_ghosts());
-    }
+    int start;  // the iteration the loop starts at (see the openings)
+    if (precond_ != QG_PRECOND_SPECTRAL) QG_CHECK(open_general(v, &start));
+    else if (cert_ && out2) QG_CHECK(open_certified(v, &start));
+    else QG_CHECK(open_alpha(v, &start));
+    if (start == CONVERGED) return QG_OK;
     // roundoff floor: a target below what the arithmetic reaches is never met.  Stop once the
     // residual has stagnated at or below 1e-10: the worst system's residual has not halved in
     // STALL_ITS iterations.  (Unpreconditioned CG decreases by only 1 - 2/sqrt(cond) per
@@ -771,33 +767,17 @@ int PcgSolver::solve(const double *in1, const double *in2, double *out1, double 
     // floor.
     const int STALL_ITS = precond_ == QG_PRECOND_NONE ? 100 : 3;
     double ref_res = 1e300;
-    int ref_it = resume ? 2 : first_it;
-    for (int it = resume ? 2 : first_it; it <= maxit_; ++it) {
-        if (resume) {  // z1 = M^-1 r1, beta, p1 = z1 + beta p0 (the tail of iteration 1)
-            resume = false;
-            QG_CHECK(precond());
-            pcg_dot_rz<<<grid, PCG_T, 0, s>>>(a, unpin);
-            QG_LAUNCH_CHECK();
-            QG_CHECK(reduce(3, s, gather, user));
-            pcg_pupdate<<<grid, PCG_T, 0, s>>>(a, 0);
-            QG_LAUNCH_CHECK();
-            QG_CHECK(fix_p_ghosts());
-        }
-        pcg_apply<<<grid, PCG_T, 0, s>>>(a);
+    int ref_it = start;
+    int status = QG_ERR_NOT_CONVERGED;
+    for (int it = start; it <= maxit_; ++it) {
+        pcg_apply<<<point_grid(a), PCG_T, 0, s>>>(a);
         QG_LAUNCH_CHECK();
-        QG_CHECK(reduce(1, s, gather, user));
-        pcg_update<<<grid, PCG_T, 0, s>>>(a);
+        QG_CHECK(reduce(PCG_S_ALPHA, v));
+        pcg_update<<<point_grid(a), PCG_T, 0, s>>>(a);
         QG_LAUNCH_CHECK();
-        QG_CHECK(reduce(2, s, gather, user));
-        QG_HIP(hipMemcpyAsync(host, a.scal, sizeof(host), hipMemcpyDeviceToHost, s));
-        QG_CHECK(comm_wait(user, s, nullptr, "PCG residual read"));
-        iters_ = it;
-        bool done = true;
-        for (int k = 0; k < 2; ++k) {
-            const double bb = host[PCG_BB + k], rr = host[PCG_RR + k];
-            relres_[k] = bb > 0 ? std::sqrt(rr / bb) : std::sqrt(rr);
-            if (!(relres_[k] <= rtol_)) done = false;
-        }
+        QG_CHECK(reduce(PCG_S_RR, v));
+        bool done;
+        QG_CHECK(read_residual(it, v, &done));
         if (done) {
             status = QG_OK;
             break;
@@ -810,15 +790,9 @@ int PcgSolver::solve(const double *in1, const double *in2, double *out1, double 
             status = QG_OK;
             break;
         }
-        QG_CHECK(precond());
-        pcg_dot_rz<<<grid, PCG_T, 0, s>>>(a, unpin);
-        QG_LAUNCH_CHECK();
-        QG_CHECK(reduce(3, s, gather, user));
-        pcg_pupdate<<<grid, PCG_T, 0, s>>>(a, 0);
-        QG_LAUNCH_CHECK();
-        QG_CHECK(fix_p_ghosts());
+        QG_CHECK(next_direction(false, v));
     }
-    pcg_backproj<<<grid, PCG_T, 0, s>>>(a);
+    pcg_backproj<<<point_grid(a), PCG_T, 0, s>>>(a);
     QG_LAUNCH_CHECK();
     return status;
 }

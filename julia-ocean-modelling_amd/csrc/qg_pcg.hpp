@@ -14,6 +14,24 @@ enum {
     PCG_NSCAL = 20
 };
 
+// what pcg_scalar derives from the (gathered) rank sums, per system (the kernel takes an int)
+enum {
+    PCG_S_BB = 0,     // ||b||^2
+    PCG_S_ALPHA = 1,  // alpha = rz / pq
+    PCG_S_RR = 2,     // ||r||^2
+    PCG_S_BETA = 3,   // beta = rz_new / rz (rz <- rz_new)
+    PCG_S_RZ0 = 4,    // initial rz
+    PCG_S_SUMR = 5,   // multigrid: sum of the Poisson residual (system 0 only)
+    PCG_S_ZPIN = 6    // multigrid: z at the pin (system 0 only)
+};
+
+// what pcg_fast_scalar derives from the openings' wider sums, per system (an int too)
+enum {
+    PCG_F_ALPHA = 0,  // (b,z), (z,Bz), (b,b) -> alpha, rz, bb: the alpha iteration
+    PCG_F_RR = 1,     // ||r1||^2 -> rr: its residual
+    PCG_F_CERT = 2    // (b,b), (r0,r0) -> bb, rr: the certified step
+};
+
 struct PcgArgs {
     int64_t M, P, ld, P_total, j_offset;
     int rank, nranks;
@@ -26,7 +44,7 @@ struct PcgArgs {
     const double *in1, *in2;
     double *out1, *out2;
     double *x[2], *r[2], *p[2], *q[2], *z[2];  // (M+2, P+2) fields
-    double *partial;                            // [blocks][2] (fast path: [blocks][6])
+    double *partial;                            // [blocks][2] (the openings: [blocks][4], [6])
     double *scal;                               // PCG_NSCAL doubles
 };
 
@@ -38,7 +56,9 @@ public:
              int pinned0, const double proj_in[4], const double proj_out[4], int precond, double rtol, int maxit,
              int chunk_rows);
     ~PcgSolver();
-    // Synchronises the stream once per iteration (convergence test on the host).
+    // The deferred form (below) is the spectral solve alone.  Otherwise: one of the three
+    // openings, the general loop from the iteration the opening names, the back-projection
+    // (DESIGN 3.4); the stream is synchronised once per iteration (convergence test on the host).
     int solve(const double *in1, const double *in2, double *out1, double *out2, int ghost_rows, hipStream_t s,
               SpectralSolver::GatherFn gather = nullptr, void *user = nullptr, HaloFn halo = nullptr,
               void *halo_user = nullptr);
@@ -67,8 +87,34 @@ public:
     int reset_latch(hipStream_t s);
 
 private:
-    int reduce(int what, hipStream_t s, SpectralSolver::GatherFn gather, void *user);
-    int mg_precond(hipStream_t s, SpectralSolver::GatherFn gather, void *user, HaloFn halo, void *halo_user);
+    struct Via {  // the stream and the transport of one solve call
+        hipStream_t s;
+        SpectralSolver::GatherFn gather;
+        void *user;
+        HaloFn halo;
+        void *halo_user;
+    };
+    // per-block partials -> rank sums -> (all-gather) -> the scalar `what` (PCG_S_*);
+    // summed: the rank's value is in scal[RSUM] already, no partials to fold
+    int reduce(int what, const Via &v, bool summed = false);
+    int mg_precond(const Via &v);
+    int precondition(const Via &v);  // z = M^-1 r
+    // the transport's ghost rows of a pair of fields (slabs; one GPU writes them itself)
+    int refresh_ghost_rows(double *f0, double *f1, const Via &v);
+    // the spectral solve of (in1, in2) into (o1, o2), projected by proj_in / proj_out, with ghosts
+    int spectral_from_input(double *o1, double *o2, const double *proj_out, const Via &v);
+    // z = M^-1 r, rz, p = z (first: the initial rz) or p = z + beta p, p's ghosts
+    int next_direction(bool first, const Via &v);
+    // the scalars to the host after iteration `it`: relres_, and whether both systems meet rtol_
+    int read_residual(int it, const Via &v, bool *done);
+    // The openings.  Each leaves the general loop's state -- x, r, p with its ghosts, rz, bb --
+    // and the iteration the loop starts at in *start: 1 after open_general, 2 after a failed
+    // certificate's restart from x0 = z0 and after a failed alpha iteration, CONVERGED when the
+    // certificate or the alpha iteration met the target (psi is written then).
+    enum { CONVERGED = 0 };
+    int open_certified(const Via &v, int *start);
+    int open_alpha(const Via &v, int *start);
+    int open_general(const Via &v, int *start);
     PcgArgs a_{};
     SpectralSolver pre_;
     MgPrecond mg_;

@@ -98,6 +98,22 @@ def test_alpha_iteration_path(env):
     assert np.linalg.norm(st.to_numpy("psi") - ref.psi) / np.linalg.norm(ref.psi) < 1e-10
 
 
+def test_alpha_iteration_failure_continues_the_loop(env):
+    """The alpha iteration with a residual target below the roundoff floor: its state is
+    materialised (x1 = alpha z0, r1, p0 = z0), the general loop continues at iteration 2 and
+    stops at its stagnation floor; the answer is unchanged (the shape, steps and bars of
+    test_certification_failure_restarts_from_z0)."""
+    torch, qg, R, O = env
+    with qg.forced_form(qg._lib.QG_FORM_PCG_NO_CERTIFICATE, 1):
+        st = qg.initialise_model(qg.bench_model(64, P=48), solver=1, pcg_rtol=1e-30, pcg_maxit=50)
+        for t in range(1, 5):
+            st.step(t)
+            s = st.stats()
+            assert s["iters"][0] >= 2 and max(s["relres"]) <= 1e-10, s
+    ref = O.State(R.bench_model(64, P=48)).run(4)
+    assert np.linalg.norm(st.to_numpy("psi") - ref.psi) / np.linalg.norm(ref.psi) < 1e-10
+
+
 @pytest.mark.parametrize("N,steps", [(64, 9), (256, 7), (1024, 5), (1280, 4)])
 def test_deferred_certificate_fused_in_tendency(env, N, steps):
     """Default (deferred) certification: no host read per step; on one GPU each solve's

@@ -56,7 +56,11 @@ double> 4527 -> 4546 instructions, tendency_pair_kernel 7516 -> 7576), so the pa
 The split of qg_capi.hip by concern (qg_capi, qg_step, qg_ctx_io, qg_ctx_comm, qg_solver: host code,
 0 functions each) with the operator entries moved into qg_ops.hip and the slot planner (qg_slots.hpp)
 left qg_ops.hip 7, qg_tracer.hip 7, qg_comm.hip 5 and qg_pcg.hip 22 identical, differing or missing
-0, new only 0, the labels equal (profiles/ctx_split/isa_diff.txt).
+0, new only 0, the labels equal (profiles/ctx_split/isa_diff.txt).  The restructured PcgSolver::solve
+(openings, one direction step, named reductions: host code) left 17 of qg_pcg.hip's 22 functions
+identical, the labels equal; the five that now share partial_tree<NV> differ, as intended, with the
+additions per value in the same order: pcg_rank_sum 186 -> 190 instructions, pcg_rank_sumN<2> 180 ->
+190, <4> 269 -> 279, <6> 357 -> 356, pcg_cert_latch_part 387 -> 388 (profiles/pcg_solve/isa_diff.txt).
 """
 import re
 import sys
