@@ -432,6 +432,63 @@ typedef struct qg_slot_call {
     qg_slot_state next;
 } qg_slot_call;
 int qg_slot_plan(const qg_slot_state *state, int kind, int64_t timestep, qg_slot_call *out);
+/* The plan of a direct (FACR) solver as the library would build it: the family of kernels the row
+ * length M gets, the transform plan, the rows per chunk, the geometry of the carry between the two
+ * passes and the layout of the solver's device memory.  Pure host function (no device needed; a
+ * test checks the rules for any shape); qg_solver_create and the contexts go through the same
+ * planner.  Not part of the drop-in surface.
+ * M: row length; P_local: this rank's rows; nranks: ranks the rows are split over; chunk_rows: the
+ * requested rows per chunk (0: automatic); f32 != 0: Float32 state; nmembers: 1, or the members of
+ * an ensemble's solver; forced_split: the value of qg_set_form(QG_FORM_ROW_SPLIT) the solve is
+ * enqueued under; cus: the device's compute units (>= 1), which only the carry variant depends on.
+ * Refusals are the solver's own: QG_ERR_UNSUPPORTED for a row length no family takes, for members
+ * on a shape without the ensemble passes and for a two-point domain on more than one rank;
+ * QG_ERR_INVALID_ARG for a chunk request that does not divide P_local or exceeds 64.
+ * A two-point domain (M = 2, or two rows in all) has family QG_SPEC_TWOPOINT and nothing else.  */
+enum { QG_SPEC_TWOPOINT = 0,   /* two points in a direction: the whole solve in one kernel        */
+       QG_SPEC_POW2 = 1,       /* M = 2^k, 8 .. 4096: row FFT and recurrences fused, in LDS       */
+       QG_SPEC_HALF = 2,       /* M = 8192: the same, one system per workgroup at half length     */
+       QG_SPEC_GEN = 3,        /* any other M <= 3200: fused passes, mixed-radix or direct DFT    */
+       QG_SPEC_SPLIT = 4,      /* ... <= 8192 (or forced): row transforms and recurrences apart   */
+       QG_SPEC_WIDE_SPLIT = 5, /* even M <= 16384: split, one system at a time at half length     */
+       QG_SPEC_WIDE_POW2 = 6,  /* M = 16384: the same on the tuned 8192-point plan                */
+       QG_SPEC_BLUESTEIN = 7   /* any M beyond, <= 2^18: chirp-z row transforms in global memory  */ };
+enum { QG_SPEC_BLK_TW = 0, QG_SPEC_BLK_COEF, QG_SPEC_BLK_HOT, /* tables: row twiddles, per-line coefficients   */
+       QG_SPEC_BLK_U, QG_SPEC_BLK_ULS, QG_SPEC_BLK_WLS, QG_SPEC_BLK_UIN, QG_SPEC_BLK_WIN, /* per-solve scratch */
+       QG_SPEC_BLK_DCPART, QG_SPEC_BLK_REC, QG_SPEC_BLK_GREC, QG_SPEC_BLK_EXT, QG_SPEC_BLK_LINE,
+       QG_SPEC_BLK_HLINE, QG_SPEC_BLK_SCAL, QG_SPEC_BLK_PINPART,
+       QG_SPEC_BLK_MEMBERS,    /* the scratch (U .. PINPART) of an ensemble's members 1 .. n-1     */
+       QG_SPEC_BLK_TW2, QG_SPEC_BLK_HALF_TMP, QG_SPEC_BLK_PERM, /* half-length twiddles, system-0 rows, reversal */
+       QG_SPEC_BLK_BL_CHIRP, QG_SPEC_BLK_BL_BHAT, QG_SPEC_BLK_BL_TW, QG_SPEC_BLK_BL_BUF0, QG_SPEC_BLK_BL_BUF1,
+       QG_SPEC_BLOCKS = 25 };
+typedef struct qg_spec_block {
+    int64_t offset, bytes; /* from the allocation's base; both multiples of 256, 0 bytes: absent  */
+} qg_spec_block;
+typedef struct qg_spec_plan {
+    int32_t family;        /* QG_SPEC_*                                                            */
+    int32_t nrad;          /* passes of the mixed-radix plan; 0: none (FFT families, direct DFT)   */
+    int32_t rad[16];       /* their radices: 8s, then 4, then 2, then odd primes <= 13             */
+    int32_t L, Nc;         /* rows per chunk and chunks: what one workgroup of a pass walks        */
+    int32_t KH, KS;        /* wavenumber lines M/2 + 1, and their stride in the tables             */
+    int32_t carry_blocks;  /* carry: blocks of 16 lines; carry_groups = that + 1 workgroups in x   */
+    int32_t carry_groups;
+    int32_t carry_variant; /* workgroups per CU the carry kernel is built for: 1 or 4              */
+    int32_t fuse_pin;      /* one rank: the carry also closes the lines (no pin kernel)            */
+    int32_t npin;          /* parts of the pin value pass B sums                                   */
+    int32_t row_groups;    /* split families: workgroups of the row transforms, min(P, 1024)       */
+    int32_t bl_L, bl_rows; /* Bluestein: transform length (2^k >= 2M - 1) and rows per batch       */
+    int32_t reserved[2];
+    int64_t length;        /* length of the planned transform: M, or M/2 for the wide split rows   */
+    int64_t member_bytes;  /* bytes of one member's scratch: blocks U .. PINPART                   */
+    int64_t total_bytes;   /* of the allocation: the end of the last block                         */
+    qg_spec_block block[QG_SPEC_BLOCKS];
+} qg_spec_plan;
+int qg_spectral_plan(int64_t M, int64_t P_local, int nranks, int chunk_rows, int f32, int nmembers,
+                     int forced_split, int cus, qg_spec_plan *out);
+/* The table of block QG_SPEC_BLK_PERM for a plan with nrad > 0: perm[k], k in [0, length), is where
+ * the plan's stages leave frequency k (digit reversal).  QG_ERR_INVALID_ARG for a plan without
+ * passes.                                                                                      */
+int qg_spectral_plan_permutation(const qg_spec_plan *plan, int32_t *perm);
 
 /* ---- stateless kernels on (M+2, P+2) device fields (ghost ring refreshed on output) ---- */
 int qg_laplace_5p(const double *u, double *out, int64_t M, int64_t P, double dx, void *stream); /* laplacian.jl:15-27 */

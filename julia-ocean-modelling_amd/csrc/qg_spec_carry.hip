@@ -374,40 +374,24 @@ __global__ __launch_bounds__(PIN_THREADS) void spec_pin(SpecArgs a) {
     }
 }
 
-// The carry launch: k-blocks plus the extra column, and the kernel variant (spec_carry<4>, two
-// workgroups per CU, when one per CU would leave a second round).  Decided from the row length
-// and the device alone -- the single solve and an ensemble's share it, so their bits agree.
-static int carry_geometry(const SpecArgs &a, unsigned *nkb, bool *two_per_cu) {
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0;
-        QG_HIP(hipGetDevice(&dev));
-        QG_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    }
-    *nkb = (unsigned)((a.KH + CARRY_KB - 1) / CARRY_KB) + 1;
-    *two_per_cu = 2 * (int)*nkb > cus;
-    return QG_OK;
-}
-
-// the carry of one context (no e) or of every member of an ensemble (grid z)
+// the carry of one context (no e) or of every member of an ensemble (grid z): the plan's
+// workgroups (k-blocks plus the extra column) and variant (spec_plan, qg_spec_plan.hpp)
 template <class... E>
-static int launch_carry_t(const SpecArgs &a, int nmembers, hipStream_t s, const E &...e) {
-    unsigned nkb = 0;
-    bool two_per_cu = false;
-    QG_CHECK(carry_geometry(a, &nkb, &two_per_cu));
-    const dim3 grid(nkb, 2, (unsigned)nmembers);
-    return two_per_cu ? launch_kernel(spec_carry<4, E...>, grid, 64 * CARRY_WAVES, 0, s, a, e...)
-                      : launch_kernel(spec_carry<1, E...>, grid, 64 * CARRY_WAVES, 0, s, a, e...);
+static int launch_carry_t(const SpecArgs &a, const qg_spec_plan &p, int nmembers, hipStream_t s, const E &...e) {
+    const dim3 grid((unsigned)p.carry_groups, 2, (unsigned)nmembers);
+    return p.carry_variant == 4 ? launch_kernel(spec_carry<4, E...>, grid, 64 * CARRY_WAVES, 0, s, a, e...)
+                                : launch_kernel(spec_carry<1, E...>, grid, 64 * CARRY_WAVES, 0, s, a, e...);
 }
 
-int launch_carry(const SpecArgs &a, hipStream_t s) { return launch_carry_t(a, 1, s); }
+int launch_carry(const SpecArgs &a, const qg_spec_plan &p, hipStream_t s) { return launch_carry_t(a, p, 1, s); }
 
-int launch_carry_members(const SpecArgs &a, const SpecEns &e, int nmembers, hipStream_t s) {
-    return launch_carry_t(a, nmembers, s, e);
+int launch_carry_members(const SpecArgs &a, const qg_spec_plan &p, const SpecEns &e, int nmembers, hipStream_t s) {
+    return launch_carry_t(a, p, nmembers, s, e);
 }
 
-int launch_carry_members(const SpecArgs &a, const SpecSweep &e, int nmembers, hipStream_t s) {
-    return launch_carry_t(a, nmembers, s, e);
+int launch_carry_members(const SpecArgs &a, const qg_spec_plan &p, const SpecSweep &e, int nmembers,
+                         hipStream_t s) {
+    return launch_carry_t(a, p, nmembers, s, e);
 }
 
 int launch_pin(const SpecArgs &a, hipStream_t s) {

@@ -1,6 +1,7 @@
 // What the spectral solver's kernel files (qg_spec_*.hip) share: the families' size constants
-// (the host side sizes its tables by them), the storage types, the ensemble member offsets and
-// the device helpers of more than one family.  Every helper is inlined or a template: each
+// (those that are host rules too come from the planner, qg_spec_plan.hpp, through
+// qg_spectral.hpp), the storage types, the ensemble member offsets and the device helpers of
+// more than one family.  Every helper is inlined or a template: each
 // file is its own code object and nothing here is called across files.
 #pragma once
 
@@ -13,10 +14,8 @@
 namespace qg {
 
 // the carry and pin kernels' geometry (qg_spec_carry.hip)
+// (CARRY_KB, PIN_THREADS, PIN_PAD: qg_spec_plan.hpp)
 constexpr int CARRY_WAVES = 8;
-constexpr int PIN_THREADS = 256;
-__host__ __device__ inline int pin_kblocks(int KH) { return (2 * KH + PIN_THREADS - 1) / PIN_THREADS; }
-constexpr int CARRY_KB = 16;
 constexpr int CARRY_SEG = CARRY_WAVES * (64 / CARRY_KB);
 constexpr int CARRY_REG = 8;  // chunks per segment held in registers
 
@@ -159,8 +158,6 @@ __device__ __forceinline__ void carry_in(const SpecArgs &a, const Coef &cf, int 
 // lanes of a pair form a + b == b + a, so every lane ends with the same bits), then the wave
 // sums in wave order through LDS.  (A serial loop of dependent scalar loads here cost one
 // memory round trip per eight parts in front of every workgroup's first row.)
-constexpr int PIN_PAD = 1024;  // >= the widest pass B workgroup
-
 template <int T>
 __device__ __forceinline__ double pin_part(const SpecArgs &a, int t) {
     static_assert(T <= PIN_PAD, "pinpart padding");
@@ -195,17 +192,16 @@ __device__ __forceinline__ void chunk_carry(const SpecArgs &a, int s, int k, int
 }
 
 // the wide rows' passes (M = 8192, qg_spec_half.hip)
-constexpr int HN = 4096;           // half-length FFT
+// (HN = 4096, the half-length FFT: qg_spec_plan.hpp)
 constexpr int HT = 512;            // threads per workgroup
 constexpr int HK = HN / HT;        // wavenumber slots per thread (k_q there); slot (q 0, t 0)
                                    // packs the real lines k = 0 (.x) and k = HN (.y)
 static_assert(HN == lx::N && HT == lx::T && HK == 8, "wide-row transform geometry");
 
 // the generic passes (qg_spec_gen.hip)
+// (GEN_MMAX, GEN_RMAX: qg_spec_plan.hpp)
 constexpr int GEN_T = 256;
-constexpr int GEN_MMAX = 3200;                               // 3 row buffers of M complex in LDS
 constexpr int GEN_KQ = (GEN_MMAX / 2 + GEN_T) / GEN_T;       // wavenumber slots per thread
-constexpr int GEN_RMAX = 13;                                 // largest radix of a planned pass
 
 // X_k = sum_x src[x] W^(k x), W = tw[1] (forward) or its conjugate (inverse)
 template <bool INV>
@@ -224,8 +220,7 @@ __device__ __forceinline__ double2 dft_at(const double2 *src, const double2 *twl
 
 // the split passes (qg_spec_gen.hip)
 constexpr int SPL_T = 512;        // row-transform threads (256 VGPRs: a radix-13 butterfly + its roots)
-constexpr int SPL_MMAX = 8192;    // one LDS buffer of M complex (128 KB)
-constexpr int SPL_WMAX = 2 * SPL_MMAX;  // even rows up to here: one system at a time, half length
+// (SPL_MMAX, SPL_WMAX: qg_spec_plan.hpp)
 constexpr int SPL_KT = 256;       // recurrence kernels: wavenumbers per workgroup
 // SPL_U_F64: the split pipeline keeps U in F64 for F32 states too.  Its U holds the raw row
 // spectra F (and then u, X) between kernels; rounding F to F32 is a second F32 rounding of
@@ -235,8 +230,6 @@ constexpr int SPL_KT = 256;       // recurrence kernels: wavenumbers per workgro
 // 0.7 eps_32 in the fused passes, which store only the filtered u (no amplification).
 
 // the Bluestein rows (qg_spec_bluestein.hip)
-constexpr int BL_T = 256;
-constexpr int64_t BL_MMAX = 1 << 18;           // rows up to 262144 points (L <= 2^19)
-constexpr size_t BL_BUF_BYTES = (size_t)1 << 28;  // per ping-pong buffer (rows per batch)
+constexpr int BL_T = 256;  // (BL_MMAX, BL_BUF_BYTES: qg_spec_plan.hpp)
 
 }  // namespace qg

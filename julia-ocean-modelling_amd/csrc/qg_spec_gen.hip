@@ -757,11 +757,11 @@ int launch_split_recurrence(bool passB, const SpecArgs &a, hipStream_t s) {
 }
 
 // the row transforms of every row, forward (rows -> U) or inverse (U -> rows)
-static int launch_split_fft(bool inv, const SpecArgs &a, hipStream_t s) {
-    const bool wsplit = a.M > SPL_MMAX;      // half-length transforms, one system at a time
-    const bool wpow2 = a.M == 2 * SPL_MMAX;  // (the tuned 8192-point plan)
-    const size_t lds = sizeof(double2) * (wpow2 ? (size_t)WPlan::LDS : (size_t)(wsplit ? a.M / 2 : a.M));
-    const unsigned rows = (unsigned)std::min<int64_t>(a.P, 1024);
+static int launch_split_fft(bool inv, const SpecArgs &a, int family, hipStream_t s) {
+    const bool wsplit = family_wide_split(family);  // half-length transforms, one system at a time
+    const bool wpow2 = family == QG_SPEC_WIDE_POW2;  // (the tuned 8192-point plan)
+    const size_t lds = sizeof(double2) * (wpow2 ? (size_t)WPlan::LDS : (size_t)spec_planned_length(a.M, family));
+    const unsigned rows = (unsigned)spec_row_groups(a.P);
     return by_precision(a, [&](auto tag) -> int {
         using S = typename decltype(tag)::type;
         if (wpow2)
@@ -775,14 +775,14 @@ static int launch_split_fft(bool inv, const SpecArgs &a, hipStream_t s) {
     });
 }
 
-int launch_split_pass(bool passB, const SpecArgs &a, hipStream_t s) {
-    if (a.M > SPL_WMAX || (a.M > SPL_MMAX && a.M % 2 != 0)) return QG_ERR_UNSUPPORTED;
+int launch_split_pass(bool passB, const SpecArgs &a, int family, hipStream_t s) {
+    if (!family_split(family)) return QG_ERR_UNSUPPORTED;
     if (!passB) {
-        QG_CHECK(launch_split_fft(false, a, s));
+        QG_CHECK(launch_split_fft(false, a, family, s));
         return launch_split_recurrence(false, a, s);
     }
     QG_CHECK(launch_split_recurrence(true, a, s));
-    return launch_split_fft(true, a, s);
+    return launch_split_fft(true, a, family, s);
 }
 
 }  // namespace qg

@@ -1,7 +1,8 @@
 // Host side of the spectral solver's kernel families: one plain function per family (each
 // defined in the qg_spec_*.hip file that holds the family's kernels -- no kernel is visible
 // outside its file), and the two helpers every one of them launches with.  qg_spectral.hip
-// picks the family by row length and calls only these.
+// dispatches on the planner's family (spec_family, qg_spec_plan.hpp: which M is whose) and
+// calls only these.
 #pragma once
 
 #include "qg_spectral.hpp"
@@ -12,22 +13,23 @@ struct SpecEns;    // qg_spec_dev.hpp: an ensemble's member strides
 struct SpecSweep;  // ... and its per-member coefficient tables
 
 // ---- passes A (passB = false) and B of one solve, by row family --------------------------
-int launch_pow2_pass(bool passB, const SpecArgs &a, hipStream_t s);       // M = 2^k, 8 .. 4096
-int launch_half_pass(bool passB, const SpecArgs &a, hipStream_t s);       // M = 8192
-int launch_gen_pass(bool passB, const SpecArgs &a, hipStream_t s);        // any M <= GEN_MMAX
-int launch_split_pass(bool passB, const SpecArgs &a, hipStream_t s);      // M <= SPL_WMAX (even above SPL_MMAX)
-int launch_bluestein_pass(bool passB, const SpecArgs &a, hipStream_t s);  // a.bl_L != 0
+int launch_pow2_pass(bool passB, const SpecArgs &a, hipStream_t s);       // QG_SPEC_POW2
+int launch_half_pass(bool passB, const SpecArgs &a, hipStream_t s);       // QG_SPEC_HALF
+int launch_gen_pass(bool passB, const SpecArgs &a, hipStream_t s);        // QG_SPEC_GEN
+// QG_SPEC_SPLIT, QG_SPEC_WIDE_SPLIT, QG_SPEC_WIDE_POW2: `family` says which
+int launch_split_pass(bool passB, const SpecArgs &a, int family, hipStream_t s);
+int launch_bluestein_pass(bool passB, const SpecArgs &a, hipStream_t s);  // QG_SPEC_BLUESTEIN
 // the split pipeline's recurrence kernels alone (the Bluestein rows run them between their
 // own transforms)
 int launch_split_recurrence(bool passB, const SpecArgs &a, hipStream_t s);
-// every member of an ensemble (F64, M = 2^k in 8 .. 2048): grid (chunks, members)
+// every member of an ensemble (spec_supports_members): grid (chunks, members)
 int launch_pow2_pass_members(bool passB, const SpecArgs &a, const SpecEns &e, int nmembers, hipStream_t s);
 int launch_pow2_pass_members(bool passB, const SpecArgs &a, const SpecSweep &e, int nmembers, hipStream_t s);
 
-// ---- between the passes ---------------------------------------------------------------------
-int launch_carry(const SpecArgs &a, hipStream_t s);
-int launch_carry_members(const SpecArgs &a, const SpecEns &e, int nmembers, hipStream_t s);
-int launch_carry_members(const SpecArgs &a, const SpecSweep &e, int nmembers, hipStream_t s);
+// ---- between the passes (the plan: the carry's workgroups and kernel variant) ----------------
+int launch_carry(const SpecArgs &a, const qg_spec_plan &p, hipStream_t s);
+int launch_carry_members(const SpecArgs &a, const qg_spec_plan &p, const SpecEns &e, int nmembers, hipStream_t s);
+int launch_carry_members(const SpecArgs &a, const qg_spec_plan &p, const SpecSweep &e, int nmembers, hipStream_t s);
 int launch_pin(const SpecArgs &a, hipStream_t s);  // more than one rank, after the record all-gather
 
 // ---- two-point domains: the whole solve, or (unit) z = A0^-1 e_1 at init ---------------------

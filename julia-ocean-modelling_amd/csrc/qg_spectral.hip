@@ -1,6 +1,9 @@
 // Spectral (FACR) direct solver for gfx950, host side -- see qg_spectral.hpp for the method.
-// Tables, device memory, and the sequence of launches of a solve; the kernels are in the
-// qg_spec_*.hip files, one per family of rows, behind the functions of qg_spec_launch.hpp.
+// Every size rule -- the row family, the transform plan, the chunk rows, the carry geometry, the
+// layout of the device memory -- is the planner's (qg_spec_plan.hpp).  Here: the tables, one
+// function each, in long double; init, which plans, allocates what the plan lists, fills and
+// binds; and the sequence of launches of a solve.  The kernels are in the qg_spec_*.hip files,
+// one per family of rows, behind the functions of qg_spec_launch.hpp.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -12,31 +15,47 @@
 
 namespace qg {
 
-// power-of-two rows 8 .. 8192 (FFT passes), any other rows 3 .. GEN_MMAX (generic passes)
-// and GEN_MMAX .. SPL_MMAX (split passes), even rows to SPL_WMAX (wide split passes), any row
-// beyond (odd above SPL_MMAX, or above SPL_WMAX) up to BL_MMAX (Bluestein rows)
-static bool bluestein_rows(int64_t M) { return M > SPL_WMAX || (M > SPL_MMAX && M % 2 != 0); }
-bool SpectralSolver::supports(int64_t M, int64_t P) {
-    if (P < 2) return false;
-    if (M >= 8 && M <= 8192 && (M & (M - 1)) == 0) return true;
-    if (M > SPL_MMAX) return M <= BL_MMAX;
-    return M >= 2 && M <= SPL_MMAX;  // (M = 2: the two-point path, one rank)
+// pass A or B of one solve by the row's family
+static int dispatch_pass(bool passB, const SpecArgs &a, int family, hipStream_t s) {
+    switch (family) {
+    case QG_SPEC_POW2: return launch_pow2_pass(passB, a, s);
+    case QG_SPEC_HALF: return launch_half_pass(passB, a, s);
+    case QG_SPEC_GEN: return launch_gen_pass(passB, a, s);
+    case QG_SPEC_BLUESTEIN: return launch_bluestein_pass(passB, a, s);
+    default: return launch_split_pass(passB, a, family, s);  // (refuses what is not a split family)
+    }
 }
 
-// pass A or B of one solve by the row's family
-static int dispatch_pass(bool passB, const SpecArgs &a, hipStream_t s) {
-    if (a.M >= 8 && a.M <= 4096 && (a.M & (a.M - 1)) == 0) return launch_pow2_pass(passB, a, s);
-    if (a.M == 8192) return launch_half_pass(passB, a, s);
-    if (a.bl_L) return launch_bluestein_pass(passB, a, s);
-    // (qg_set_form(QG_FORM_ROW_SPLIT, 1): generic-size rows through the split passes too)
-    if (a.M > GEN_MMAX || form(QG_FORM_ROW_SPLIT)) return launch_split_pass(passB, a, s);
-    return launch_gen_pass(passB, a, s);
+// ---- tables (long double on the host) ---------------------------------------------------------
+// row twiddles exp(-2 pi i m / M)
+static std::vector<double2> row_twiddles(int64_t M) {
+    const long double twopi = 6.283185307179586476925286766559L;
+    std::vector<double2> tw(M);
+    for (int64_t m = 0; m < M; ++m) {
+        const long double ang = twopi * (long double)m / (long double)M;
+        tw[m] = make_double2((double)cosl(ang), (double)-sinl(ang));
+    }
+    return tw;
+}
+
+// the half-length transform's: exp(-2 pi i m / (M/2)) = tw[2m]
+static std::vector<double2> half_twiddles(const std::vector<double2> &tw) {
+    std::vector<double2> tw2(tw.size() / 2);
+    for (size_t m = 0; m < tw2.size(); ++m) tw2[m] = tw[2 * m];
+    return tw2;
+}
+
+static std::vector<int> plan_permutation(const qg_spec_plan &p) {
+    std::vector<int> perm(p.length);
+    spec_digit_reversal(p.length, p.nrad, p.rad, perm.data());
+    return perm;
 }
 
 // Bluestein tables (long double on the host): the chirp, and the filter's length-L transform
 // (an iterative radix-2 FFT in long double, scaled by 1/L)
-static void bl_tables(int64_t M, int L, std::vector<double2> &chirp, std::vector<double2> &bhat,
+static void bl_tables(int64_t M, const qg_spec_plan &p, std::vector<double2> &chirp, std::vector<double2> &bhat,
                       std::vector<double2> &twL) {
+    const int L = p.bl_L;
     const long double pi = 3.141592653589793238462643383279503L;
     chirp.resize(M);
     std::vector<long double> br(L, 0.0L), bi(L, 0.0L);
@@ -82,21 +101,6 @@ static void bl_tables(int64_t M, int L, std::vector<double2> &chirp, std::vector
         twL[m] = make_double2((double)cosl(a), (double)-sinl(a));
     }
 }
-
-// Rows per chunk: at most 16 (chunk summaries stay a small fraction of the traffic; 32 for
-// the wide rows, whose passes run two workgroups per chunk and whose summaries are twice as
-// long), small enough that the P / L workgroups of passes A and B cover the 256 CUs, and
-// dividing P.
-static int pick_chunk(int64_t M, int64_t P, int req) {
-    if (req > 0) return (P % req == 0 && req <= 64) ? req : -1;
-    int cap = M >= 2 * HN ? 32 : 16;
-    while (cap > 1 && P / cap < 256) cap >>= 1;
-    for (int L = cap; L >= 1; L >>= 1)
-        if (P % L == 0) return L;
-    return 1;
-}
-
-static size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // The per-(system, k) coefficients [2][KS] of the solves with shifts alpha[2] on a's geometry
 // (M, P, P_total, L, KH, KS, dx, pinned0), in long double.  Once per solver; once per member for
@@ -147,221 +151,158 @@ static void fill_hot(const std::vector<Coef> &coef, int KS, double *hot) {
     }
 }
 
-int SpectralSolver::init(int64_t M, int64_t P, int64_t P_total, int rank, int nranks, double dx,
-                         const double alpha[2], int pinned0, const double pin_in[4], const double pin_out[4],
-                         int chunk_rows, int f32, int nmembers) {
-    if (!supports(M, P)) return QG_ERR_UNSUPPORTED;
-    if (nmembers < 1 || (nmembers > 1 && !supports_members(M, P, nranks, f32))) return QG_ERR_UNSUPPORTED;
-    if (!(dx > 0) || nranks < 1 || rank < 0 || rank >= nranks || P_total != P * nranks) return QG_ERR_INVALID_ARG;
-    // two points in a direction (global): the reference's laplacian_1d_periodic
-    // (laplacian.jl:40-45) writes its wrap entry over the neighbour entry, so its matrix is not
-    // the periodic 5-point operator the passes below diagonalise -- solved as the reference
-    // builds it by spec_twopoint (one rank: a two-row domain split over ranks has one-row slabs)
-    if (M == 2 || P_total == 2) return init_twopoint(M, P, nranks, dx, alpha, pinned0, pin_in, pin_out, f32);
-    const int L = pick_chunk(M, P, chunk_rows);
-    if (L < 1) return QG_ERR_INVALID_ARG;
-    SpecArgs &a = a_;
+// The slot-order copies of r and (r, 1/r) for the lane-exchange passes (M = 4096 and 8192,
+// qg_fft_lx.hpp), whose 512 threads keep u and these in the order they hold the lines: slot
+// t + 512 q is thread t's line q.  A thread's first four lines are those of its mirror group g,
+// k = g + 512 q; the wide rows' other four are the mirrored group's, k = (512 - g) + 512 q (g = 0:
+// its own).  hot[8 KS ..): (r, 1/r) [2][KS] (scrr), hot[12 KS ..): r [2][KS] (scr).
+static void fill_hot_slots(int lines, const std::vector<Coef> &coef, int KS, double *hot) {
+    for (int s = 0; s < 2; ++s)
+        for (int t = 0; t < lx::T; ++t)
+            for (int q = 0; q < lines; ++q) {  // per thread and system
+                const int g = lx::mirror_group(t), gm = g == 0 ? 0 : 512 - g;
+                const size_t k = (size_t)((q < 4 ? g : gm) + 512 * q), slot = (size_t)(t + 512 * q);
+                const Coef &cf = coef[(size_t)s * KS + k];
+                hot[8 * KS + 2 * (s * KS + slot)] = cf.r;
+                hot[8 * KS + 2 * (s * KS + slot) + 1] = cf.rinv;
+                hot[12 * KS + s * KS + slot] = cf.r;
+            }
+}
+
+// the hot tables of coef: k order [8 KS] (fill_hot), then slot order [6 KS] (fill_hot_slots)
+static std::vector<double> hot_tables(int64_t M, const qg_spec_plan &p, const std::vector<Coef> &coef) {
+    std::vector<double> hot(14 * (size_t)p.KS);
+    fill_hot(coef, p.KS, hot.data());
+    fill_hot_slots(spec_slot_lines(M), coef, p.KS, hot.data());
+    return hot;
+}
+
+template <class T>
+T *SpectralSolver::block(int b) const {
+    const qg_spec_block &k = plan_.block[b];
+    return k.bytes ? reinterpret_cast<T *>(static_cast<char *>(mem_) + k.offset) : nullptr;
+}
+
+// host data -> the device block it was sized for
+template <class T>
+static int upload(T *dst, const std::vector<T> &v) {
+    QG_HIP(hipMemcpy(dst, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice));
+    return QG_OK;
+}
+
+// what init and init_twopoint bind alike: the shape, the ranks and the projections
+static void bind_shape(SpecArgs &a, int64_t M, int64_t P, int64_t P_total, int rank, int nranks, int f32, double dx,
+                       int pinned0, const double pin_in[4], const double pin_out[4]) {
     a.M = M;
     a.P = P;
     a.ld = M + 2;
     a.P_total = P_total;
     a.rank = rank;
     a.nranks = nranks;
-    a.L = L;
-    a.Nc = (int)(P / L);
     a.f32 = f32;
-    a.KH = (int)(M / 2 + 1);
-    a.KS = (a.KH + 63) & ~63;
-    a.nrad = 0;
-    // generic rows: mixed-radix plan, or none (direct DFT: rows with a prime factor > 13, and
-    // short rows, where the direct DFT measured no slower -- 120^2: 15 600-17 200 vs 15 000 steps/s)
-    const bool blue = bluestein_rows(M);
-    const bool wsplit = M > SPL_MMAX && !blue;  // (planned at the half length H = M/2)
-    if (!blue && (wsplit || ((M & (M - 1)) != 0 && M > 128))) {
-        int64_t m = wsplit ? M / 2 : M, n = 0;
-        int rad[16];
-        while (m % 8 == 0) { rad[n++] = 8; m /= 8; }
-        if (m % 4 == 0) { rad[n++] = 4; m /= 4; }
-        if (m % 2 == 0) { rad[n++] = 2; m /= 2; }
-        for (int p = 3; p <= GEN_RMAX && m > 1; p += 2)
-            while (m % p == 0 && n < 16) { rad[n++] = p; m /= p; }
-        if (m == 1) {
-            a.nrad = (int)n;
-            for (int i = 0; i < n; ++i) a.rad[i] = rad[i];
-        }
-    }
     a.dx = dx;
     a.pinned0 = pinned0 ? 1 : 0;
     std::memcpy(a.pin_in, pin_in, sizeof(a.pin_in));
     std::memcpy(a.pin_out, pin_out, sizeof(a.pin_out));
-    const int KS = a.KS;
+}
 
-    // ---- tables (long double) --------------------------------------------------------
-    std::vector<double2> tw(M);
-    const long double twopi = 6.283185307179586476925286766559L;
-    for (int64_t m = 0; m < M; ++m) {
-        const long double ang = twopi * (long double)m / (long double)M;
-        tw[m] = make_double2((double)cosl(ang), (double)-sinl(ang));
-    }
+int SpectralSolver::init(int64_t M, int64_t P, int64_t P_total, int rank, int nranks, double dx,
+                         const double alpha[2], int pinned0, const double pin_in[4], const double pin_out[4],
+                         int chunk_rows, int f32, int nmembers) {
+    // ---- arguments ---------------------------------------------------------------------
+    SpecShape sh{M, P, nranks, chunk_rows, f32, nmembers, 0};
+    QG_CHECK(spec_supported(sh));
+    if (!(dx > 0) || nranks < 1 || rank < 0 || rank >= nranks || P_total != P * nranks) return QG_ERR_INVALID_ARG;
+    // ---- plan (the device is asked one thing, once: its CUs, for the carry variant) ------
+    int dev = 0;
+    QG_HIP(hipGetDevice(&dev));
+    QG_HIP(hipDeviceGetAttribute(&sh.cus, hipDeviceAttributeMultiprocessorCount, dev));
+    qg_spec_plan &p = plan_;
+    QG_CHECK(spec_plan(sh, form(QG_FORM_ROW_SPLIT) != 0, p));
+    SpecArgs &a = a_;
+    bind_shape(a, M, P, P_total, rank, nranks, f32, dx, pinned0, pin_in, pin_out);
+    // two points in a direction (global): the reference's laplacian_1d_periodic
+    // (laplacian.jl:40-45) writes its wrap entry over the neighbour entry, so its matrix is not
+    // the periodic 5-point operator the passes below diagonalise -- solved as the reference
+    // builds it by spec_twopoint
+    if (p.family == QG_SPEC_TWOPOINT) return init_twopoint(alpha);
+    a.L = p.L;
+    a.Nc = p.Nc;
+    a.KH = p.KH;
+    a.KS = p.KS;
+    a.nrad = p.nrad;
+    std::memcpy(a.rad, p.rad, sizeof(int) * p.nrad);
+    a.bl_L = p.bl_L;
+    a.bl_rows = p.bl_rows;
+    a.rec_stride = rec_size(p.KS);
+    a.csc = -(dx * dx) / (double)M;
+
+    // ---- tables (long double) ----------------------------------------------------------
+    const std::vector<double2> tw = row_twiddles(M);
     std::vector<Coef> coef;
     QG_CHECK(build_coef(a, alpha, coef));
-
-    // ---- device memory ---------------------------------------------------------------
-    const size_t n_tw = align_up(sizeof(double2) * M);
-    const size_t n_coef = align_up(sizeof(Coef) * coef.size());
-    const size_t n_hot = align_up(sizeof(double) * 14 * (size_t)KS);
-    const size_t n_U = align_up(sizeof(double2) * (size_t)P * 2 * KS);
-    const size_t n_S = align_up(sizeof(double2) * (size_t)a.Nc * 2 * KS);
-    const size_t n_dc = align_up(sizeof(double) * a.Nc);
-    const int64_t RS = rec_size(KS, P);
-    const size_t n_rec = align_up(sizeof(double) * RS);
-    const size_t n_grec = align_up(sizeof(double) * RS * nranks);  // gather target (also 1-rank ring)
-    const size_t n_ext = align_up(sizeof(double2) * 4 * KS);
-    const size_t n_line = align_up(sizeof(double) * P);  // (hline and line)
-    const size_t n_scal = align_up(sizeof(double) * 8);
-    const int nkb = (a.KH + CARRY_KB - 1) / CARRY_KB;  // carry k-blocks (fused pin parts)
-    // zero-padded to PIN_PAD parts: every pass B thread loads one unconditionally (pin_part)
-    const size_t n_pinpart = align_up(sizeof(double) * (std::max({pin_kblocks(a.KH), nkb, PIN_PAD}) + 1));
-    const bool wide = M == 2 * HN;  // wide-row passes: half-length twiddles + system-0 rows
-    const size_t n_tw2 = (wide || wsplit) ? align_up(sizeof(double2) * (size_t)(M / 2)) : 0;
-    const size_t n_half = wide ? align_up((f32 ? sizeof(float) : sizeof(double)) * (size_t)P * M) : 0;
-    // split passes with a plan: where the DIF stages leave frequency k (digit reversal)
-    const int64_t MP = wsplit ? M / 2 : M;  // length of the planned transform
-    const size_t n_perm = a.nrad > 0 ? align_up(sizeof(int) * MP) : 0;
     std::vector<double2> bl_chirp, bl_bhat, bl_twL;
-    int BL = 0, brows = 0;
-    if (blue) {
-        BL = 1;
-        while (BL < 2 * M - 1) BL <<= 1;
-        brows = (int)std::max<int64_t>(1, std::min<int64_t>(P, (int64_t)(BL_BUF_BYTES / (sizeof(double2) * BL))));
-        bl_tables(M, BL, bl_chirp, bl_bhat, bl_twL);
-    }
-    const size_t n_bl = blue ? align_up(sizeof(double2) * M) + 2 * align_up(sizeof(double2) * BL) +
-                                   2 * align_up(sizeof(double2) * (size_t)BL * brows)
-                             : 0;
-    // an ensemble's members 1 .. nmembers-1: a copy each of the block U .. pinpart, behind member 0's
-    const size_t n_member = n_U + 4 * n_S + n_dc + n_rec + n_grec + n_ext + 2 * n_line + n_scal + n_pinpart;
-    const size_t n_more = (size_t)(nmembers - 1) * n_member;
+    if (p.bl_L) bl_tables(M, p, bl_chirp, bl_bhat, bl_twL);
+
+    // ---- device memory: the plan's blocks ----------------------------------------------
     nmembers_ = nmembers;
-    member_bytes_ = n_member;
-    bytes_ = n_tw + n_coef + n_hot + n_member + n_more + n_tw2 + n_half + n_perm + n_bl;
+    bytes_ = (size_t)p.total_bytes;
     if (hipMalloc(&mem_, bytes_) != hipSuccess) {
         mem_ = nullptr;
         return QG_ERR_ALLOC;
     }
-    char *p = static_cast<char *>(mem_);
-    auto take = [&](size_t n) { char *r = p; p += n; return r; };
-    double2 *d_tw = (double2 *)take(n_tw);
-    Coef *d_coef = (Coef *)take(n_coef);
-    double *d_hot = (double *)take(n_hot);
-    a.U = take(n_U);  // double2 (F64 states) or float2 (F32) per element
-    a.ULS = (double2 *)take(n_S);
-    a.WLS = (double2 *)take(n_S);
-    a.UIN = (double2 *)take(n_S);
-    a.WIN = (double2 *)take(n_S);
-    a.dcpart = (double *)take(n_dc);
-    a.rec = (double *)take(n_rec);
-    grec_buf_ = (double *)take(n_grec);
+    double *hot = block<double>(QG_SPEC_BLK_HOT);
+    a.tw = block<double2>(QG_SPEC_BLK_TW);
+    a.coef = block<Coef>(QG_SPEC_BLK_COEF);
+    a.crr = reinterpret_cast<const double2 *>(hot);
+    a.ccs = hot + 4 * p.KS;
+    a.cr = hot + 6 * p.KS;
+    a.scrr = reinterpret_cast<const double2 *>(hot + 8 * p.KS);
+    a.scr = hot + 12 * p.KS;
+    a.U = block<char>(QG_SPEC_BLK_U);  // double2 (F64 states) or float2 (F32) per element
+    a.ULS = block<double2>(QG_SPEC_BLK_ULS);
+    a.WLS = block<double2>(QG_SPEC_BLK_WLS);
+    a.UIN = block<double2>(QG_SPEC_BLK_UIN);
+    a.WIN = block<double2>(QG_SPEC_BLK_WIN);
+    a.dcpart = block<double>(QG_SPEC_BLK_DCPART);
+    a.rec = block<double>(QG_SPEC_BLK_REC);
+    grec_buf_ = block<double>(QG_SPEC_BLK_GREC);
     a.grec = nranks > 1 ? grec_buf_ : a.rec;
-    a.rec_stride = RS;
-    a.EXT = (double2 *)take(n_ext);
-    a.line = (double *)take(n_line);
-    a.hline = (double *)take(n_line);
-    a.scal = (double *)take(n_scal);
-    a.pinpart = (double *)take(n_pinpart);
-    char *more = take(n_more);
-    a.tw2 = (wide || wsplit) ? (const double2 *)take(n_tw2) : nullptr;
-    a.half_tmp = wide ? (void *)take(n_half) : nullptr;
-    a.perm = nullptr;
-    if (a.nrad > 0) {
-        int *d_perm = (int *)take(n_perm);
-        std::vector<int> perm(MP);
-        for (int64_t k = 0; k < MP; ++k) {
-            int64_t rem = k, span = MP, pos = 0;
-            for (int q = 0; q < a.nrad; ++q) {
-                span /= a.rad[q];
-                pos += (rem % a.rad[q]) * span;
-                rem /= a.rad[q];
-            }
-            perm[k] = (int)pos;
-        }
-        QG_HIP(hipMemcpy(d_perm, perm.data(), sizeof(int) * MP, hipMemcpyHostToDevice));
-        a.perm = d_perm;
+    a.EXT = block<double2>(QG_SPEC_BLK_EXT);
+    a.line = block<double>(QG_SPEC_BLK_LINE);
+    a.hline = block<double>(QG_SPEC_BLK_HLINE);
+    a.scal = block<double>(QG_SPEC_BLK_SCAL);
+    a.pinpart = block<double>(QG_SPEC_BLK_PINPART);
+    a.tw2 = block<double2>(QG_SPEC_BLK_TW2);
+    a.half_tmp = block<char>(QG_SPEC_BLK_HALF_TMP);
+    a.perm = block<int>(QG_SPEC_BLK_PERM);
+    a.bl_chirp = block<double2>(QG_SPEC_BLK_BL_CHIRP);
+    a.bl_bhat = block<double2>(QG_SPEC_BLK_BL_BHAT);
+    a.bl_tw = block<double2>(QG_SPEC_BLK_BL_TW);
+    a.bl_buf0 = block<double2>(QG_SPEC_BLK_BL_BUF0);
+    a.bl_buf1 = block<double2>(QG_SPEC_BLK_BL_BUF1);
+
+    // ---- uploads, and the zeros the first solve reads ----------------------------------
+    if (a.perm) QG_CHECK(upload(block<int>(QG_SPEC_BLK_PERM), plan_permutation(p)));
+    if (p.bl_L) {
+        QG_CHECK(upload(block<double2>(QG_SPEC_BLK_BL_CHIRP), bl_chirp));
+        QG_CHECK(upload(block<double2>(QG_SPEC_BLK_BL_BHAT), bl_bhat));
+        QG_CHECK(upload(block<double2>(QG_SPEC_BLK_BL_TW), bl_twL));
     }
-    a.bl_L = 0;
-    if (blue) {
-        double2 *ch = (double2 *)take(align_up(sizeof(double2) * M));
-        double2 *bh = (double2 *)take(align_up(sizeof(double2) * BL));
-        double2 *tl = (double2 *)take(align_up(sizeof(double2) * BL));
-        a.bl_buf0 = (double2 *)take(align_up(sizeof(double2) * (size_t)BL * brows));
-        a.bl_buf1 = (double2 *)take(align_up(sizeof(double2) * (size_t)BL * brows));
-        QG_HIP(hipMemcpy(ch, bl_chirp.data(), sizeof(double2) * M, hipMemcpyHostToDevice));
-        QG_HIP(hipMemcpy(bh, bl_bhat.data(), sizeof(double2) * BL, hipMemcpyHostToDevice));
-        QG_HIP(hipMemcpy(tl, bl_twL.data(), sizeof(double2) * BL, hipMemcpyHostToDevice));
-        a.bl_chirp = ch;
-        a.bl_bhat = bh;
-        a.bl_tw = tl;
-        a.bl_L = BL;
-        a.bl_rows = brows;
-    }
-    a.tw = d_tw;
-    a.coef = d_coef;
-    QG_HIP(hipMemcpy(d_tw, tw.data(), sizeof(double2) * M, hipMemcpyHostToDevice));
-    if (wide || wsplit) {  // exp(-2 pi i m / (M/2)) = tw[2m]
-        const int64_t H = M / 2;
-        std::vector<double2> tw2(H);
-        for (int64_t m = 0; m < H; ++m) tw2[m] = tw[2 * m];
-        QG_HIP(hipMemcpy((void *)a.tw2, tw2.data(), sizeof(double2) * H, hipMemcpyHostToDevice));
-    }
-    QG_HIP(hipMemcpy(d_coef, coef.data(), sizeof(Coef) * coef.size(), hipMemcpyHostToDevice));
-    {
-        // [2][KS] (r, 1/r) pairs, [2][KS] cs, [2][KS] r; slot order: [2][KS] (r, 1/r), [2][KS] r
-        std::vector<double> hot(14 * (size_t)KS);
-        fill_hot(coef, KS, hot.data());
-        if (M == lx::N || M == 2 * lx::N) {
-            const int lines = M == lx::N ? 4 : 8;  // per thread and system
-            for (int s = 0; s < 2; ++s)
-                for (int t = 0; t < lx::T; ++t)
-                    for (int q = 0; q < lines; ++q) {
-                        const int g = lx::mirror_group(t), gm = g == 0 ? 0 : 512 - g;
-                        const size_t k = (size_t)((q < 4 ? g : gm) + 512 * q), slot = (size_t)(t + 512 * q);
-                        const Coef &cf = coef[(size_t)s * KS + k];
-                        hot[8 * KS + 2 * (s * KS + slot)] = cf.r;
-                        hot[8 * KS + 2 * (s * KS + slot) + 1] = cf.rinv;
-                        hot[12 * KS + s * KS + slot] = cf.r;
-                    }
-        }
-        QG_HIP(hipMemcpy(d_hot, hot.data(), sizeof(double) * hot.size(), hipMemcpyHostToDevice));
-        a.crr = reinterpret_cast<const double2 *>(d_hot);
-        a.ccs = d_hot + 4 * KS;
-        a.cr = d_hot + 6 * KS;
-        a.scrr = reinterpret_cast<const double2 *>(d_hot + 8 * KS);
-        a.scr = d_hot + 12 * KS;
-        a.csc = -(dx * dx) / (double)M;
-    }
-    QG_HIP(hipMemset(a.rec, 0, n_rec));
-    QG_HIP(hipMemset(a.scal, 0, n_scal));
-    QG_HIP(hipMemset(a.line, 0, n_line));
-    QG_HIP(hipMemset(a.pinpart, 0, n_pinpart));
-    if (n_more) QG_HIP(hipMemset(more, 0, n_more));  // (the same zeros, and the rest, per member)
+    QG_CHECK(upload(block<double2>(QG_SPEC_BLK_TW), tw));
+    if (a.tw2) QG_CHECK(upload(block<double2>(QG_SPEC_BLK_TW2), half_twiddles(tw)));
+    QG_CHECK(upload(block<Coef>(QG_SPEC_BLK_COEF), coef));
+    QG_CHECK(upload(hot, hot_tables(M, p, coef)));
+    // (the other members' scratch whole: the same zeros, and the rest, per member)
+    for (int b : {QG_SPEC_BLK_REC, QG_SPEC_BLK_SCAL, QG_SPEC_BLK_LINE, QG_SPEC_BLK_PINPART, QG_SPEC_BLK_MEMBERS})
+        if (p.block[b].bytes) QG_HIP(hipMemset(block<char>(b), 0, (size_t)p.block[b].bytes));
     return QG_OK;
 }
 
-int SpectralSolver::init_twopoint(int64_t M, int64_t P, int nranks, double dx, const double alpha[2], int pinned0,
-                                  const double pin_in[4], const double pin_out[4], int f32) {
-    if (nranks != 1) return QG_ERR_UNSUPPORTED;
+int SpectralSolver::init_twopoint(const double alpha[2]) {
     SpecArgs &a = a_;
-    a.M = M;
-    a.P = P;
-    a.ld = M + 2;
-    a.P_total = P;
-    a.rank = 0;
-    a.nranks = 1;
-    a.f32 = f32;
-    a.dx = dx;
-    a.pinned0 = pinned0 ? 1 : 0;
-    std::memcpy(a.pin_in, pin_in, sizeof(a.pin_in));
-    std::memcpy(a.pin_out, pin_out, sizeof(a.pin_out));
+    const int64_t M = a.M, P = a.P;
+    const double dx = a.dx;
     a.two = 1;
     a.two_yline = P != 2 ? 1 : 0;  // (M = P = 2: the line along x, of two points)
     const int64_t N = a.two_yline ? P : M;
@@ -381,8 +322,8 @@ int SpectralSolver::init_twopoint(int64_t M, int64_t P, int nranks, double dx, c
                 a.two_inv1mrN[s][q] = (double)(-1 / expm1l((long double)N * logl(r)));
             }
         }
-    const size_t n_X = align_up(sizeof(double) * 4 * (size_t)N), n_z = align_up(sizeof(double) * 2 * (size_t)N);
-    const size_t n_scal = align_up(sizeof(double) * 8);
+    const size_t n_X = spec_align(sizeof(double) * 4 * (size_t)N), n_z = spec_align(sizeof(double) * 2 * (size_t)N);
+    const size_t n_scal = spec_align(sizeof(double) * 8);
     bytes_ = n_X + n_z + n_scal;
     if (hipMalloc(&mem_, bytes_) != hipSuccess) {
         mem_ = nullptr;
@@ -414,8 +355,9 @@ int SpectralSolver::init_member_tables(const double *alpha1, const double *pin_i
     if (!alpha1 || !pin_in || sweep_mem_) return QG_ERR_INVALID_ARG;
     if (a_.two || !supports_members(a_.M, a_.P, a_.nranks, a_.f32)) return QG_ERR_UNSUPPORTED;
     const int KS = a_.KS;
-    const size_t n_coef = align_up(sizeof(Coef) * 2 * (size_t)KS), n_hot = align_up(sizeof(double) * 8 * (size_t)KS);
-    const size_t n_tab = n_coef + n_hot, n_pin = align_up(sizeof(double) * 4 * (size_t)nmembers_);
+    const size_t n_coef = spec_align(sizeof(Coef) * 2 * (size_t)KS);
+    const size_t n_hot = spec_align(sizeof(double) * 8 * (size_t)KS);
+    const size_t n_tab = n_coef + n_hot, n_pin = spec_align(sizeof(double) * 4 * (size_t)nmembers_);
     std::vector<char> host(n_tab * (size_t)nmembers_ + n_pin, 0);
     std::vector<Coef> coef;
     for (int b = 0; b < nmembers_; ++b) {
@@ -453,29 +395,23 @@ int SpectralSolver::solve(const void *in1, const void *in2, void *out1, void *ou
     a.out2 = out2;
     a.write_ghost_rows = write_ghost_rows;
     if (a.two) return launch_twopoint(a, 0, s);
-    // one rank: the carry kernel closes the lines itself (no spec_pin), with or without a
-    // transport -- a 1-rank ring's record all-gather would only copy the record onto itself
-    // (grec aliases rec), so none is posted (r04: RCCL's one-rank all-gather was a 6 us copy
-    // kernel and spec_pin another launch on the 1-rank ring's critical path)
-    a.fuse_pin = a.nranks == 1 ? 1 : 0;
-    a.npin = a.fuse_pin ? (a.KH + CARRY_KB - 1) / CARRY_KB : pin_kblocks(a.KH);
-    QG_CHECK(dispatch_pass(false, a, s));
-    QG_CHECK(launch_carry(a, s));
+    a.fuse_pin = plan_.fuse_pin;  // (one rank: the carry also closes the lines, no spec_pin)
+    a.npin = plan_.npin;
+    // (qg_set_form(QG_FORM_ROW_SPLIT, 1), as it stands now: generic rows through the split passes)
+    const int family = spec_family(a.M, form(QG_FORM_ROW_SPLIT) != 0);
+    QG_CHECK(dispatch_pass(false, a, family, s));
+    QG_CHECK(launch_carry(a, plan_, s));
     if (a.nranks > 1) {
         if (!gather) return QG_ERR_RCCL;
         QG_CHECK(gather(user, a.rec, grec_buf_, a.rec_stride, s));
     }
     if (!a.fuse_pin) QG_CHECK(launch_pin(a, s));
-    return dispatch_pass(true, a, s);
-}
-
-bool SpectralSolver::supports_members(int64_t M, int64_t P, int nranks, int f32) {
-    return nranks == 1 && !f32 && P >= 3 && M >= 8 && M <= 2048 && (M & (M - 1)) == 0;
+    return dispatch_pass(true, a, family, s);
 }
 
 // The solve of every member of an ensemble: the launches of solve() on one rank (pass A, the
-// carry with the fused pin, pass B), each over all members.  The carry variant is chosen as
-// solve() chooses it, from (M, P) alone.
+// carry with the fused pin, pass B), each over all members.  The carry variant is solve()'s:
+// the plan's.
 int SpectralSolver::solve_members(const void *in1, const void *in2, void *out1, void *out2, int64_t field_stride_bytes,
                                   hipStream_t s) {
     if (!mem_) return QG_ERR_NOT_BOUND;
@@ -487,12 +423,12 @@ int SpectralSolver::solve_members(const void *in1, const void *in2, void *out1, 
     a.out1 = out1;
     a.out2 = out2;
     a.write_ghost_rows = 1;
-    a.fuse_pin = 1;
-    a.npin = (a.KH + CARRY_KB - 1) / CARRY_KB;
-    const SpecEns e{(int64_t)member_bytes_, field_stride_bytes};
+    a.fuse_pin = plan_.fuse_pin;  // (one rank)
+    a.npin = plan_.npin;
+    const SpecEns e{plan_.member_bytes, field_stride_bytes};
     auto run = [&](const auto &pack) -> int {
         QG_CHECK(launch_pow2_pass_members(false, a, pack, nmembers_, s));
-        QG_CHECK(launch_carry_members(a, pack, nmembers_, s));
+        QG_CHECK(launch_carry_members(a, plan_, pack, nmembers_, s));
         return launch_pow2_pass_members(true, a, pack, nmembers_, s);
     };
     if (!sweep_mem_) return run(e);
@@ -509,3 +445,16 @@ int SpectralSolver::solve_members(const void *in1, const void *in2, void *out1, 
 }
 
 }  // namespace qg
+
+// the plan alone, for a caller-supplied CU count and row-split form (qg_mi355.h)
+extern "C" int qg_spectral_plan(int64_t M, int64_t P_local, int nranks, int chunk_rows, int f32, int nmembers,
+                                int forced_split, int cus, qg_spec_plan *out) {
+    if (!out) return QG_ERR_INVALID_ARG;
+    return qg::spec_plan(qg::SpecShape{M, P_local, nranks, chunk_rows, f32, nmembers, cus}, forced_split != 0, *out);
+}
+
+extern "C" int qg_spectral_plan_permutation(const qg_spec_plan *plan, int32_t *perm) {
+    if (!plan || !perm || plan->nrad < 1 || plan->nrad > 16) return QG_ERR_INVALID_ARG;
+    qg::spec_digit_reversal(plan->length, plan->nrad, plan->rad, perm);
+    return QG_OK;
+}

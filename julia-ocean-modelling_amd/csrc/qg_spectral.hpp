@@ -28,15 +28,17 @@
 #pragma once
 
 #include "qg_common.hpp"
+#include "qg_spec_plan.hpp"
 
 namespace qg {
 
-struct Coef {  // per (system, k); see SpectralSolver::init
+struct Coef {  // per (system, k); see build_coef (qg_spectral.hip)
     double r, rinv, lr, q, gam, rP, gamP, cs, inv1mrPt, qm1;  // qm1 = r^(L-1)
 };
+static_assert(sizeof(Coef) == SPEC_COEF_BYTES && sizeof(double2) == SPEC_COMPLEX_BYTES, "the planner's sizes");
 
 struct SpecArgs {
-    int64_t M, P, ld;         // M = row length (2^k, or even <= 2048), P = local rows, ld = M + 2
+    int64_t M, P, ld;         // M = row length (2 .. 2^18: spec_family), P = local rows, ld = M + 2
     int64_t P_total;          // global rows
     int rank, nranks;
     int L, Nc, KH, KS;        // chunk rows, chunks, M/2+1, padded k stride
@@ -86,7 +88,8 @@ struct SpecArgs {
     double2 *bl_buf0, *bl_buf1;  // [bl_rows][bl_L] ping-pong
     int bl_L, bl_rows;        // bl_L = 0: not a Bluestein row
     // (M+2, P+2) fields, or null: pass A also writes its two inputs there, ghost ring included
-    // (single GPU) -- the drop-in lean mode's move of the new zeta into slot 1 (qg_capi.hip)
+    // (single GPU) -- the drop-in lean mode's move of the new zeta into slot 1 (plan_solve,
+    // qg_slots.hpp)
     void *zcopy1, *zcopy2;
     int npin;                 // pin parts pass B sums (pinpart[0 .. npin))
     // two-point domains (global M = 2 or P = 2, one rank): see spec_twopoint
@@ -107,7 +110,7 @@ __host__ __device__ inline int64_t rec_UIN0(int KS) { return 10 * (int64_t)KS; }
 // [0] sum of the k = 0 Poisson line (-> delta), [1] H = its local total, [2] Q = sum of its
 // local prefix sums (the singular line's cross-rank affine correction), [3] unused
 __host__ __device__ inline int64_t rec_DSUM(int KS) { return 12 * (int64_t)KS; }
-__host__ __device__ inline int64_t rec_size(int KS, int64_t P) { (void)P; return 12 * (int64_t)KS + 4; }
+// (the record's length, rec_size: qg_spec_plan.hpp)
 
 class SpectralSolver {
 public:
@@ -116,7 +119,7 @@ public:
              int pinned0, const double pin_in[4], const double pin_out[4], int chunk_rows, int f32 = 0,
              int nmembers = 1);  // nmembers > 1: an ensemble's solver (supports_members, solve_members)
     ~SpectralSolver();
-    static bool supports(int64_t M, int64_t P);
+    static bool supports(int64_t M, int64_t P) { return spec_supports(M, P); }
     // enqueue the whole solve; `gather` (may be null) all-gathers rec -> grec across ranks
     typedef int (*GatherFn)(void *user, const double *send, double *recv, int64_t count, hipStream_t s);
     int solve(const void *in1, const void *in2, void *out1, void *out2, int write_ghost_rows,
@@ -126,7 +129,9 @@ public:
     // Ensembles: nmembers solves per launch, member b's fields field_stride_bytes * b behind the
     // given ones (in1 .. out2: member 0's), every member with its own scratch and the shared
     // tables.  Same chunking and per-point arithmetic as solve(): bit-identical per member.
-    static bool supports_members(int64_t M, int64_t P, int nranks, int f32);
+    static bool supports_members(int64_t M, int64_t P, int nranks, int f32) {
+        return spec_supports_members(M, P, nranks, f32);
+    }
     int solve_members(const void *in1, const void *in2, void *out1, void *out2, int64_t field_stride_bytes,
                       hipStream_t s);
     // Members with their own Helmholtz shift (after init with nmembers): alpha1[b] replaces
@@ -135,20 +140,21 @@ public:
     int init_member_tables(const double *alpha1, const double *pin_in);
     int members() const { return nmembers_; }
     // pass A can write the zcopy fields (power-of-two rows: the FFT and wide-row passes)
-    bool fuses_input_copy() const { return !a_.two && a_.M >= 8 && a_.M <= 8192 && (a_.M & (a_.M - 1)) == 0; }
+    bool fuses_input_copy() const { return family_fft(plan_.family); }
     const SpecArgs &args() const { return a_; }
     size_t device_bytes() const { return bytes_; }
     double *gather_buf() const { return grec_buf_; }  // the record all-gather's target
 
 private:
-    int init_twopoint(int64_t M, int64_t P, int nranks, double dx, const double alpha[2], int pinned0,
-                      const double pin_in[4], const double pin_out[4], int f32);
+    int init_twopoint(const double alpha[2]);
+    template <class T>
+    T *block(int b) const;  // block b of the plan's arena (null: absent)
     SpecArgs a_{};
+    qg_spec_plan plan_{};  // family QG_SPEC_TWOPOINT (0) until init: no pass of the others is enqueued
     void *mem_ = nullptr;
     double *grec_buf_ = nullptr;
     size_t bytes_ = 0;
-    int nmembers_ = 1;         // scratch blocks (U .. pinpart) allocated
-    size_t member_bytes_ = 0;  // bytes of one
+    int nmembers_ = 1;         // scratch blocks (U .. pinpart) allocated, plan_.member_bytes apart
     void *sweep_mem_ = nullptr;  // per-member coefficient tables and pin_in (init_member_tables)
     size_t sweep_tables_ = 0;    // bytes of one member's tables
     size_t sweep_hot_ = 0;       // offset of crr | ccs | cr in them

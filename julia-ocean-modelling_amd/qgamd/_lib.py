@@ -43,6 +43,13 @@ QG_TEND_AUTO, QG_TEND_RING, QG_TEND_DIRECT, QG_TEND_ONE_POINT = 0, 1, 2, 3
 QG_TEND_KERNEL_RING, QG_TEND_KERNEL_PAIR, QG_TEND_KERNEL_DIRECT = 0, 1, 2
 QG_SLOT_CALL_TENDENCY, QG_SLOT_CALL_SOLVE, QG_SLOT_CALL_SETTLE, QG_SLOT_CALL_CANONICALIZE = 0, 1, 2, 3
 QG_SLOT_AFTER_NONE, QG_SLOT_AFTER_MOVE, QG_SLOT_AFTER_DEFER = 0, 1, 2
+# qg_spectral_plan: the row families and the blocks of the solver's device memory, in order
+(QG_SPEC_TWOPOINT, QG_SPEC_POW2, QG_SPEC_HALF, QG_SPEC_GEN, QG_SPEC_SPLIT, QG_SPEC_WIDE_SPLIT, QG_SPEC_WIDE_POW2,
+ QG_SPEC_BLUESTEIN) = range(8)
+QG_SPEC_BLOCK_NAMES = ("tw", "coef", "hot", "U", "ULS", "WLS", "UIN", "WIN", "dcpart", "rec", "grec", "EXT", "line",
+                       "hline", "scal", "pinpart", "members", "tw2", "half_tmp", "perm", "bl_chirp", "bl_bhat",
+                       "bl_tw", "bl_buf0", "bl_buf1")
+QG_SPEC_BLOCKS = len(QG_SPEC_BLOCK_NAMES)
 
 
 class QgParams(C.Structure):
@@ -118,6 +125,21 @@ class QgSlotCall(C.Structure):
                 ("next", QgSlotState)]
 
 
+class QgSpecBlock(C.Structure):
+    _fields_ = [("offset", C.c_int64), ("bytes", C.c_int64)]
+
+
+class QgSpecPlan(C.Structure):
+    """Mirror of ``struct qg_spec_plan``: qg_spectral_plan's plan of one direct solver."""
+
+    _fields_ = [("family", C.c_int32), ("nrad", C.c_int32), ("rad", C.c_int32 * 16), ("L", C.c_int32),
+                ("Nc", C.c_int32), ("KH", C.c_int32), ("KS", C.c_int32), ("carry_blocks", C.c_int32),
+                ("carry_groups", C.c_int32), ("carry_variant", C.c_int32), ("fuse_pin", C.c_int32),
+                ("npin", C.c_int32), ("row_groups", C.c_int32), ("bl_L", C.c_int32), ("bl_rows", C.c_int32),
+                ("reserved", C.c_int32 * 2), ("length", C.c_int64), ("member_bytes", C.c_int64),
+                ("total_bytes", C.c_int64), ("block", QgSpecBlock * QG_SPEC_BLOCKS)]
+
+
 class QgStats(C.Structure):
     _fields_ = [("iters", C.c_int32 * 2), ("relres", C.c_double * 2), ("delta", C.c_double),
                 ("pin", C.c_double)]
@@ -176,6 +198,9 @@ SIGNATURES = [
     ("qg_tendency_plan", C.c_int, [_i64, C.c_int * 4, C.c_int, C.c_int, C.c_int, C.c_int, _i64,
                                    C.POINTER(QgTendPlan)]),
     ("qg_slot_plan", C.c_int, [C.POINTER(QgSlotState), C.c_int, _i64, C.POINTER(QgSlotCall)]),
+    ("qg_spectral_plan", C.c_int, [_i64, _i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                   C.POINTER(QgSpecPlan)]),
+    ("qg_spectral_plan_permutation", C.c_int, [C.POINTER(QgSpecPlan), C.POINTER(C.c_int32)]),
     ("qg_laplace_5p", C.c_int, [_dp, _dp, _i64, _i64, C.c_double, _vp]),
     ("qg_cd", C.c_int, [_dp, _dp, _i64, _i64, C.c_double, _vp]),
     ("qg_arakawa_J", C.c_int, [_dp, _dp, _dp, _i64, _i64, C.c_double, _vp]),

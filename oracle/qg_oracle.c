@@ -303,6 +303,12 @@ int qgo_solve(long M, long P, double dx, double alpha, int pinned, const double 
      * cancellation (absolute error ~eps against (2 pi / P)^2: 2e-9 relative psi error on a
      * 256 x 32768 Poisson problem against a long-double solve, tools/r06/solve_precision.py) */
     double *sx = malloc(sizeof(double) * (size_t)M), *sy = malloc(sizeof(double) * (size_t)P);
+    if (!sx || !sy) {
+        free(sx);
+        free(sy);
+        free(g);
+        return -1;
+    }
     for (long k = 0; k < M; ++k) { const double t = sin(M_PI * (double)k / (double)M); sx[k] = t * t; }
     for (long k = 0; k < P; ++k) { const double t = sin(M_PI * (double)k / (double)P); sy[k] = t * t; }
     for (long ky = 0; ky < P; ++ky)

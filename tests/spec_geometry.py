@@ -1,8 +1,9 @@
-"""What a solve of the direct (FACR) solver reaches in y, restated in Python from
-csrc/qg_spectral.hip (pick_chunk, SpectralSolver::init, dispatch_pass), qg_spec_carry.hip
-(spec_carry, local_line, carry_geometry), qg_spec_gen.hip (launch_split_fft),
-qg_spec_bluestein.hip (bl_rows) and qg_spec_dev.hpp (the size constants), and the case lists of
-tests/test_gpu_solver_geometry.py.
+"""What a solve of the direct (FACR) solver reaches in y, restated in Python: the host rules of
+the planner csrc/qg_spec_plan.hpp (spec_family, spec_radices, pick_chunk, the carry geometry,
+spec_arena -- tests/test_spec_geometry_cpu.py compares this model with the library's
+qg_spectral_plan case by case, by value), the kernels' own geometry from qg_spec_carry.hip
+(spec_carry, local_line), qg_spec_gen.hip (the row loops) and qg_spec_bluestein.hip (bl_rows),
+and the case lists of tests/test_gpu_solver_geometry.py.
 
 The x geometry of a solve is its row family (family()): which transform and which pass kernels
 a row length M gets.  The y geometry is
@@ -17,7 +18,7 @@ a row length M gets.  The y geometry is
                    CARRY_SEG = 32 segments of SL = ceil(Nc / 32) chunks; a segment's summaries
                    sit in registers while SL <= CARRY_REG = 8 (Nc <= 256) and are streamed from
                    memory otherwise.  The kernel variant (spec_carry<1> or <4>) follows the
-                   number of carry workgroups against the device's CUs (carry_geometry).
+                   number of carry workgroups against the device's CUs (spec_plan).
   line tiles       local_line tiles the singular k = 0 Poisson line in 64 * CARRY_WAVES *
                    LINE_PER = 4096 rows, with running carries between tiles.
   row trips        the split and wide transforms launch min(P, 1024) workgroups, each looping
@@ -29,7 +30,7 @@ a row length M gets.  The y geometry is
 All of P above is the rank's P_local.
 """
 
-# ---- constants of the sources (tests/test_spec_geometry_cpu.py pins them) ------------------
+# ---- constants of the sources (tests/test_spec_geometry_cpu.py holds them to the planner) ----
 CARRY_WAVES = 8
 CARRY_KB = 16
 CARRY_SEG = CARRY_WAVES * (64 // CARRY_KB)  # 32
@@ -43,7 +44,9 @@ SPL_MMAX = 8192
 SPL_WMAX = 2 * SPL_MMAX
 BL_MMAX = 1 << 18
 BL_BUF_BYTES = 1 << 28
-FFT_ROW_GROUPS = 1024                       # launch_split_fft: min(P, 1024) workgroups
+FFT_ROW_GROUPS = 1024                       # SPL_ROW_GROUPS: min(P, 1024) transform workgroups
+PIN_THREADS, PIN_PAD = 256, 1024
+ENS_MMAX = 2048                             # an ensemble's members: power-of-two rows up to here
 CHUNK_CAP, CHUNK_CAP_WIDE, CHUNK_REQ_MAX, CHUNK_MIN_GROUPS = 16, 32, 64, 256
 PLAN_ABOVE = 128                            # generic rows: a mixed-radix plan only above this M
 MI355X_CUS = 256
@@ -84,21 +87,30 @@ def pick_chunk(M, P, req=0):
     return 1
 
 
-def planned(m):
-    """SpectralSolver::init's plan rule on a transform length m: radices 8, 4, 2 and the odd
-    primes up to GEN_RMAX must exhaust it."""
+def radices(m):
+    """The mixed-radix plan of a transform length m: 8s, then 4, then 2, then the odd primes up to
+    GEN_RMAX; [] unless they exhaust it."""
+    rad = []
     while m % 8 == 0:
+        rad.append(8)
         m //= 8
     if m % 4 == 0:
+        rad.append(4)
         m //= 4
     if m % 2 == 0:
+        rad.append(2)
         m //= 2
     p = 3
     while p <= GEN_RMAX and m > 1:
         while m % p == 0:
+            rad.append(p)
             m //= p
         p += 2
-    return m == 1
+    return rad if m == 1 else []
+
+
+def planned(m):
+    return bool(radices(m))
 
 
 def is_pow2(M):
@@ -158,6 +170,130 @@ def carry_variant(M, cus=MI355X_CUS):
     """carry_geometry: two workgroups per CU (spec_carry<4>) when one per CU leaves a second round."""
     KH = M // 2 + 1
     return MINW4 if 2 * (ceil_div(KH, CARRY_KB) + 1) > cus else MINW1
+
+
+# ---- the whole plan, as qg_spectral_plan reports it ------------------------------------------
+OK, INVALID_ARG, UNSUPPORTED = 0, -1, -2
+# QG_SPEC_*: the family codes of include/qg_mi355.h (planned or direct: nrad)
+TWOPOINT, F_POW2, F_HALF, F_GEN, F_SPLIT, F_WIDE_SPLIT, F_WIDE_POW2, F_BLUESTEIN = range(8)
+BLOCKS = ("tw", "coef", "hot", "U", "ULS", "WLS", "UIN", "WIN", "dcpart", "rec", "grec", "EXT", "line", "hline",
+          "scal", "pinpart", "members", "tw2", "half_tmp", "perm", "bl_chirp", "bl_bhat", "bl_tw", "bl_buf0",
+          "bl_buf1")
+MEMBER_BLOCKS = BLOCKS[BLOCKS.index("U"):BLOCKS.index("pinpart") + 1]
+PLAN_FIELDS = ("family", "nrad", "rad", "L", "Nc", "KH", "KS", "carry_blocks", "carry_groups", "carry_variant",
+               "fuse_pin", "npin", "row_groups", "bl_L", "bl_rows", "length", "member_bytes", "total_bytes", "block")
+
+
+def family_code(name):
+    return {"pow2": F_POW2, "half": F_HALF, "gen": F_GEN, "split": F_SPLIT, "bluestein": F_BLUESTEIN}.get(
+        name.split("_")[0], F_WIDE_POW2 if name == "wide_pow2" else F_WIDE_SPLIT)
+
+
+def supports(M, P):
+    return P >= 2 and 2 <= M <= BL_MMAX
+
+
+def supports_members(M, P, nranks, f32):
+    return nranks == 1 and not f32 and P >= 3 and is_pow2(M) and 8 <= M <= ENS_MMAX
+
+
+def align_up(x):
+    return (x + 255) & ~255
+
+
+def arena(M, P, nranks, f32, nmembers, fam, L, nrad):
+    """The device allocation of SpectralSolver::init, restated from its size arithmetic as it stood
+    before the planner (the n_* of qg_spectral.hip and the order of its take() calls):
+    ([(offset, bytes)] per BLOCKS, member bytes, total)."""
+    KH = M // 2 + 1
+    KS = (KH + 63) & ~63
+    Nc = P // L
+    blue = fam == "bluestein"
+    wsplit = fam in WIDE_FAMILIES
+    wide = M == 2 * HN
+    n_tw = align_up(16 * M)
+    n_coef = align_up(80 * 2 * KS)                        # sizeof(Coef): ten doubles
+    n_hot = align_up(8 * 14 * KS)
+    n_U = align_up(16 * P * 2 * KS)
+    n_S = align_up(16 * Nc * 2 * KS)
+    n_dc = align_up(8 * Nc)
+    RS = 12 * KS + 4
+    n_rec = align_up(8 * RS)
+    n_grec = align_up(8 * RS * nranks)
+    n_ext = align_up(16 * 4 * KS)
+    n_line = align_up(8 * P)
+    n_scal = align_up(8 * 8)
+    nkb = ceil_div(KH, CARRY_KB)
+    n_pinpart = align_up(8 * (max(ceil_div(2 * KH, PIN_THREADS), nkb, PIN_PAD) + 1))
+    n_tw2 = align_up(16 * (M // 2)) if (wide or wsplit) else 0
+    n_half = align_up((4 if f32 else 8) * P * M) if wide else 0
+    MP = M // 2 if wsplit else M
+    n_perm = align_up(4 * MP) if nrad > 0 else 0
+    bl = [0] * 5
+    if blue:
+        BL, brows, _, _ = bluestein(M, P)
+        bl = [align_up(16 * M), align_up(16 * BL), align_up(16 * BL), align_up(16 * BL * brows),
+              align_up(16 * BL * brows)]
+    n_member = n_U + 4 * n_S + n_dc + n_rec + n_grec + n_ext + 2 * n_line + n_scal + n_pinpart
+    n_more = (nmembers - 1) * n_member
+    total = n_tw + n_coef + n_hot + n_member + n_more + n_tw2 + n_half + n_perm + sum(bl)
+    sizes = [n_tw, n_coef, n_hot, n_U, n_S, n_S, n_S, n_S, n_dc, n_rec, n_grec, n_ext, n_line, n_line, n_scal,
+             n_pinpart, n_more, n_tw2, n_half, n_perm] + bl
+    out, off = [], 0
+    for n in sizes:                                       # (take(): a running pointer)
+        out.append((off, n))
+        off += n
+    return out, n_member, total
+
+
+def plan(M, P, nranks=1, req=0, f32=0, nmembers=1, forced=False, cus=MI355X_CUS):
+    """(status, dict of PLAN_FIELDS or None): SpectralSolver::init's refusals in its order, then
+    every figure a solver of that shape is built from."""
+    if not supports(M, P):
+        return UNSUPPORTED, None
+    if nmembers < 1 or (nmembers > 1 and not supports_members(M, P, nranks, f32)):
+        return UNSUPPORTED, None
+    if nranks < 1 or cus < 1:
+        return INVALID_ARG, None
+    zero = dict.fromkeys(PLAN_FIELDS, 0)
+    zero.update(rad=[0] * 16, block=[(0, 0)] * len(BLOCKS))
+    if M == 2 or P * nranks == 2:
+        return (OK, dict(zero, family=TWOPOINT)) if nranks == 1 else (UNSUPPORTED, None)
+    L = pick_chunk(M, P, req)
+    if L < 1:
+        return INVALID_ARG, None
+    fam = family(M, forced)
+    KH = M // 2 + 1
+    length = M // 2 if fam in WIDE_FAMILIES else M
+    rad = radices(length) if (fam in WIDE_FAMILIES or (fam[:3] in ("gen", "spl") and M > PLAN_ABOVE)) else []
+    if fam.endswith(("_planned", "_direct")):
+        assert bool(rad) == fam.endswith("_planned"), (M, fam, rad)
+    d = dict(zero, family=family_code(fam), nrad=len(rad), rad=rad + [0] * (16 - len(rad)), L=L, Nc=P // L, KH=KH,
+             KS=(KH + 63) & ~63, length=length)
+    d["carry_blocks"] = ceil_div(KH, CARRY_KB)
+    d["carry_groups"] = d["carry_blocks"] + 1
+    d["carry_variant"] = 4 if carry_variant(M, cus) == MINW4 else 1
+    d["fuse_pin"] = int(nranks == 1)
+    d["npin"] = d["carry_blocks"] if nranks == 1 else ceil_div(2 * KH, PIN_THREADS)
+    if fam in SPLIT_FAMILIES + WIDE_FAMILIES:
+        d["row_groups"] = min(P, FFT_ROW_GROUPS)
+    if fam == "bluestein":
+        d["bl_L"], d["bl_rows"] = bluestein(M, P)[:2]
+    d["block"], d["member_bytes"], d["total_bytes"] = arena(M, P, nranks, f32, nmembers, fam, L, len(rad))
+    return OK, d
+
+
+def digit_reversal(length, rad):
+    """Where the plan's DIF stages leave frequency k."""
+    perm = []
+    for k in range(length):
+        rem, span, pos = k, length, 0
+        for r in rad:
+            span //= r
+            pos += (rem % r) * span
+            rem //= r
+        perm.append(pos)
+    return perm
 
 
 def three(n):

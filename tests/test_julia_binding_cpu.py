@@ -131,7 +131,8 @@ def test_the_binding_covers_the_drop_in_surface():
     # the CPU tests call, the host-transport attach (a Julia caller would pass @cfunction
     # pointers; RCCL is the Julia path) and the flattened duplicate of qg_get_stats
     assert set(c_prototypes()) - bound == {"qg_comm_exchange_plan", "qg_tendency_plan", "qg_slot_plan",
-                                           "qg_comm_init_host", "qg_solver_stats"}
+                                           "qg_spectral_plan", "qg_spectral_plan_permutation", "qg_comm_init_host",
+                                           "qg_solver_stats"}
 
 
 JL_OF_C = {"double": "Float64", "int64_t": "Int64", "int32_t": "Int32"}

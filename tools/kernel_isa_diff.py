@@ -61,6 +61,13 @@ left qg_ops.hip 7, qg_tracer.hip 7, qg_comm.hip 5 and qg_pcg.hip 22 identical, d
 identical, the labels equal; the five that now share partial_tree<NV> differ, as intended, with the
 additions per value in the same order: pcg_rank_sum 186 -> 190 instructions, pcg_rank_sumN<2> 180 ->
 190, <4> 269 -> 279, <6> 357 -> 356, pcg_cert_latch_part 387 -> 388 (profiles/pcg_solve/isa_diff.txt).
+The spectral solver's planner (csrc/qg_spec_plan.hpp: the row family, the transform plan, the chunk
+rows, the carry geometry and the arena as host rules; the size constants moved there from
+qg_spec_dev.hpp; launchers taking the family and the plan beside SpecArgs, whose layout is
+untouched) left all 128 functions of the solver's files identical, differing or missing 0, new only
+0, the labels equal file by file (bluestein 15, carry 7, gen 22, half 6, pow2 40, pow2_ens 36,
+twopoint 2, qg_spectral.hip 0), and qg_pcg.hip's 22 identical, qg_ensemble.hip 0 functions
+(profiles/spec_plan/isa_diff.txt).
 """
 import re
 import sys
