@@ -76,7 +76,26 @@ typedef enum {
 typedef enum {
     QG_F64 = 0,             /* IEEE Float64 state: the reference's arithmetic              */
     QG_F32 = 1              /* Float32 state (BASELINE config 5); transforms and y-solves  *
-                             * still run in F64, the fields and u are stored in F32         */
+                             * still run in F64, the fields and u are stored in F32.        *
+                             * The tendency (qg_evolve_zeta) evaluates the expressions of   *
+                             * evolve_zeta! in the reference's grouping entirely in float,  *
+                             * one IEEE rounding per operation (no contraction, IEEE       *
+                             * division), the same in every kernel form.  Rounded from      *
+                             * double to float once each: dx, dt, visc, U, r, beta_1,       *
+                             * beta_2 (derived in double), the wind row value w_j, and      *
+                             * 23/12, 16/12, 5/12 (each quotient taken in double).  Formed  *
+                             * in float from the rounded dx: idx = 1/dx, idx2 = idx*idx,    *
+                             * cdc = 0.5*idx, den = 12*(dx*dx).  Then, in float:            *
+                             *   lap(u) = ((((w + e) - 4*c) + s) + n) * idx2                *
+                             *   v = visc * lap(lap(psi)),  J = ((jpp + jpt) + jtp) / den   *
+                             *   b = beta_l * (cdc * (psi_e - psi_w))                       *
+                             *   last = U * (cdc * (zeta_e - zeta_w))   (layer 1)           *
+                             *        = r * lap(psi)                    (layer 2)           *
+                             *   F = ((v - J) - b) - last,  layer 1 with wind: F = F + w_j  *
+                             *   Euler: zeta + (dt * F)                                     *
+                             *   AB3:   zeta + dt * (((c23*F) - (c16*F1)) + (c5*F2))        *
+                             * tests/tend32_model.py restates this in numpy; the device is  *
+                             * held to it byte for byte.                                    */
 } qg_dtype;
 
 typedef enum {

@@ -252,6 +252,10 @@ BALANCED_CASES = [(520, 13), (1032, 13)]
 # the fused tendency against numpy on prescribed arrays: (W, M, P, R)
 REF_CASES = [(64, 67, 5, 1), (64, 68, 7, 2), (64, 130, 13, 1), (64, 200, 13, 4), (64, 258, 12, 5),
              (128, 258, 13, 4), (256, 514, 13, 4), (512, 1026, 13, 4)]
+# the direct kernel alone against numpy below REF_CASES: (M, P) with its M < 8 wrap (a true
+# modulo) on and off, and P = 2, 3, where every row at j +- 2 is a wrapped row.  The direct kernel
+# is the yardstick of every tile test down to M = 2.
+REF_SMALL_CASES = [(2, 2), (2, 3), (3, 2), (3, 3), (4, 3), (5, 4), (7, 5), (8, 3)]
 # the pair kernel's smallest shapes with interior strips
 PAIR_CASES = [(1030, 13), (1030, 7), (1026, 13), (1536, 12), (514, 9)]
 # the certifying tendency

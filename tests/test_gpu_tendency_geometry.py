@@ -6,7 +6,8 @@ case lists; tests/test_tendency_geometry_cpu.py proves the lists reach every bod
     a non-default P_fwd, and the balanced geometry, against the cache-resident direct kernel:
     zeta, psi and f_store np.array_equal after Euler, Euler, AB3 x 3, ghost ring included;
   * the fused tendency on prescribed arrays against the numpy restatement of evolve_zeta!
-    (oracle/qg_ref.py, the grouping of model.jl:123-170), Euler and AB3, bit for bit;
+    (oracle/qg_ref.py, the grouping of model.jl:123-170), Euler and AB3, bit for bit; the
+    direct kernel, the yardstick of the rest, also around its M < 8 wrap and at P = 2, 3;
   * the F32 pair kernel at the smallest shapes with interior strips;
   * the certifying tendency: the same states as the direct form, and a certificate that is the
     residual -- on a psi perturbed at one point, against numpy to a relative 1e-10;
@@ -158,7 +159,7 @@ def _check_against_numpy(torch, qg, R, M, P, what):
 def test_direct_tendency_against_numpy(env):
     torch, qg, R = env
     L = qg._lib
-    for M, P in sorted({(M, P) for _, M, P, _ in G.REF_CASES}):
+    for M, P in sorted({(M, P) for _, M, P, _ in G.REF_CASES} | set(G.REF_SMALL_CASES)):
         with qg.forced_form(L.QG_FORM_TENDENCY, L.QG_TEND_DIRECT):
             _check_against_numpy(torch, qg, R, M, P, f"direct (M, P) = {(M, P)}")
 
