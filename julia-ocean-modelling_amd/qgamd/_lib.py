@@ -22,6 +22,8 @@ QG_TRACERS_MAX, QG_TRC_LINES = 8, 6
 QG_TRC_FORM_AUTO, QG_TRC_FORM_RING, QG_TRC_FORM_ONE_POINT = 0, 1, 2
 QG_FLT_LINES, QG_FLOATS_MAX_PER_LAYER = 8, 1 << 26
 QG_FLT_PSI, QG_FLT_ZETA = 0, 1
+QG_TSTATS_MEAN, QG_TSTATS_EDDY = 0, 1
+QG_TSTATS_FIELDS, QG_TSTATS_LAYER_FIELDS, QG_TSTATS_SUM_LINES = 26, 11, 12
 
 
 def QG_TRC_FORM_RING_TILE(w, r):
@@ -271,6 +273,19 @@ SIGNATURES = [
     ("qg_floats_sample", C.c_int, [_vp, C.c_int, _dp]),
     ("qg_floats_get_state", C.c_int, [_vp, C.POINTER(_i64), C.POINTER(C.c_int)]),
     ("qg_floats_set_state", C.c_int, [_vp, _i64, C.c_int]),
+    # include/qg_mi355_tstats.h (outputs and checkpoint arrays: device pointers)
+    ("qg_tstats_create", C.c_int, [_vp, C.c_int, C.POINTER(_vp)]),
+    ("qg_ens_tstats_create", C.c_int, [_vp, C.c_int, C.POINTER(_vp)]),
+    ("qg_tstats_destroy", C.c_int, [_vp]),
+    ("qg_tstats_reset", C.c_int, [_vp]),
+    ("qg_tstats_accumulate", C.c_int, [_vp]),
+    ("qg_tstats_run", C.c_int, [_vp, _i64, _i64, _i64]),
+    ("qg_tstats_count", C.c_int, [_vp, C.POINTER(_i64)]),
+    ("qg_tstats_field", C.c_int, [_vp, C.c_int, _dp]),
+    ("qg_tstats_summary", C.c_int, [_vp, _dp]),
+    ("qg_tstats_raw_doubles", C.c_int, [_vp, C.POINTER(_i64)]),
+    ("qg_tstats_save", C.c_int, [_vp, _dp]),
+    ("qg_tstats_load", C.c_int, [_vp, _dp, _i64]),
 ]
 
 _lib = None

@@ -1204,6 +1204,136 @@ def float_positions(pos, dx, wrap=False):
     return out * dx
 
 
+TSTATS_LAYER_FIELDS = ("mean_psi", "mean_zeta", "mean_u", "mean_v", "var_psi", "var_zeta", "var_u", "var_v",
+                       "cov_u_v", "cov_u_zeta", "cov_v_zeta")
+TSTATS_FIELDS = (tuple(f"{n}_{l}" for l in (1, 2) for n in TSTATS_LAYER_FIELDS)
+                 + ("mean_tau", "mean_vb", "var_tau", "cov_vb_tau"))
+"""The 26 fields of include/qg_mi355_tstats.h in index order (layers 1-based, as the reference
+counts them): per layer the time means of psi, zeta, u, v, their variances, the Reynolds stress
+<u'v'> and the eddy vorticity fluxes <u'zeta'>, <v'zeta'>; then tau = psi_1 - psi_2,
+vb = (v_1 + v_2) / 2, var tau and the eddy heat flux <vb'tau'>.  u and v are the centred-difference
+velocities of psi: the eddy flow, without the model's U."""
+
+TSTATS_SUMMARY_LINES = ("mke_1", "mke_2", "eke_1", "eke_2", "mean_enstrophy_1", "mean_enstrophy_2",
+                        "eddy_enstrophy_1", "eddy_enstrophy_2", "mean_ape", "eddy_ape", "heat_flux", "n")
+
+
+def tstats_field_names():
+    """The names :meth:`TimeStats.field` accepts, in the header's index order."""
+    return TSTATS_FIELDS
+
+
+class TimeStats:
+    """Running time statistics of a :class:`State` or of every member of an :class:`Ensemble`
+    (include/qg_mi355_tstats.h): time means, variances and eddy covariances as fields, accumulated
+    on the device sample by sample with Welford's recurrence in float64, bit for bit the header's
+    contract in numpy.  The owner is never written.
+
+    ``level="eddy"`` keeps all 26 fields of :func:`tstats_field_names`; ``level="mean"`` only
+    ``mean_psi`` and ``mean_zeta`` of both layers, at a fifth of the memory traffic.  One rank,
+    M and P >= 3; F64 or F32 states, uniform or sweep ensembles.  Close it before its owner."""
+
+    def __init__(self, owner, level="eddy"):
+        torch = _torch()
+        self.owner = owner
+        self.level = {"mean": _lib.QG_TSTATS_MEAN, "eddy": _lib.QG_TSTATS_EDDY}[level]
+        self.device = owner.device
+        self.nmembers = getattr(owner, "nmembers", None)
+        self._ts = C.c_void_p()
+        with torch.cuda.device(self.device):
+            if self.nmembers is None:
+                call("qg_tstats_create", owner._ctx, self.level, C.byref(self._ts))
+            else:
+                call("qg_ens_tstats_create", owner._ens, self.level, C.byref(self._ts))
+
+    def close(self):
+        """Destroy the library handle and its accumulators now (qg_tstats_destroy)."""
+        ts = getattr(self, "_ts", None)
+        if ts and _lib._lib is not None:
+            _lib._lib.qg_tstats_destroy(ts)
+            self._ts = None
+
+    def __del__(self):
+        self.close()
+
+    def _lead(self):
+        return () if self.nmembers is None else (self.nmembers,)
+
+    def _out(self, shape):
+        torch = _torch()
+        return torch.empty(self._lead() + shape, dtype=torch.float64, device=self.owner.psi.device)
+
+    def reset(self):
+        """qg_tstats_reset: n = 0, every accumulator +0.0."""
+        with _torch().cuda.device(self.device):
+            call("qg_tstats_reset", self._ts)
+        return self
+
+    def accumulate(self):
+        """qg_tstats_accumulate: one sample of the owner's newest state.  Not synchronised."""
+        with _torch().cuda.device(self.device):
+            call("qg_tstats_accumulate", self._ts)
+
+    def run(self, first_step, nsteps, every=1):
+        """qg_tstats_run: ``nsteps`` steps of the owner, one sample after every ``every``-th."""
+        with _torch().cuda.device(self.device):
+            call("qg_tstats_run", self._ts, int(first_step), int(nsteps), int(every))
+
+    @property
+    def count(self):
+        """qg_tstats_count: the samples since the last :meth:`reset` (or the n of :meth:`load`)."""
+        n = C.c_int64()
+        call("qg_tstats_count", self._ts, C.byref(n))
+        return n.value
+
+    def field(self, field):
+        """qg_tstats_field: one field by name (:func:`tstats_field_names`) or index as a
+        ([B,] P+2, M+2) float64 device tensor with its periodic ghost ring: a mean as stored, a
+        variance or covariance as C / (n - 1) (0 for n = 1).  Not synchronised."""
+        k = TSTATS_FIELDS.index(field) if isinstance(field, str) else int(field)
+        m = self.owner.model
+        out = self._out((m.P + 2, m.M + 2))
+        with _torch().cuda.device(self.device):
+            call("qg_tstats_field", self._ts, k, _ptr(out))
+        return out
+
+    def summary(self):
+        """qg_tstats_summary: the ([B,] 12) record of :data:`TSTATS_SUMMARY_LINES` (eddy level)."""
+        out = self._out((_lib.QG_TSTATS_SUM_LINES,))
+        with _torch().cuda.device(self.device):
+            call("qg_tstats_summary", self._ts, _ptr(out))
+        return out
+
+    def save(self):
+        """qg_tstats_save: ``(raw, n)``, the accumulators as an opaque float64 device tensor and
+        the count, for :meth:`load` of a handle of the same owner shape and level."""
+        torch = _torch()
+        nd = C.c_int64()
+        call("qg_tstats_raw_doubles", self._ts, C.byref(nd))
+        raw = torch.empty((nd.value,), dtype=torch.float64, device=self.owner.psi.device)
+        with torch.cuda.device(self.device):
+            call("qg_tstats_save", self._ts, _ptr(raw))
+        return raw, self.count
+
+    def load(self, raw, n):
+        """qg_tstats_load: resume from :meth:`save`."""
+        torch = _torch()
+        nd = C.c_int64()
+        call("qg_tstats_raw_doubles", self._ts, C.byref(nd))
+        if raw.dtype != torch.float64 or raw.numel() != nd.value or not raw.is_contiguous() or not raw.is_cuda:
+            raise ValueError(f"expected a contiguous float64 device tensor of {nd.value} elements")
+        with torch.cuda.device(self.device):
+            call("qg_tstats_load", self._ts, _ptr(raw), int(n))
+        return self
+
+
+def eke(ts):
+    """The eddy kinetic energy map of a :class:`TimeStats` at the eddy level: 1/2 (var u + var v)
+    per layer, a ([B,] 2, P+2, M+2) device tensor."""
+    torch = _torch()
+    return torch.stack([0.5 * (ts.field(f"var_u_{l}") + ts.field(f"var_v_{l}")) for l in (1, 2)], dim=-3)
+
+
 PROFILE_LINES = ("energy_1", "energy_2", "enstrophy_1", "enstrophy_2", "interface", "psi_mean_1", "psi_mean_2",
                  "zeta_mean_1", "zeta_mean_2", "vort_flux_1", "vort_flux_2", "heat_flux")
 """The rows of a profiles record (layers 1-based, as the reference counts them), each a function

@@ -67,7 +67,8 @@ qg_spec_dev.hpp; launchers taking the family and the plan beside SpecArgs, whose
 untouched) left all 128 functions of the solver's files identical, differing or missing 0, new only
 0, the labels equal file by file (bluestein 15, carry 7, gen 22, half 6, pow2 40, pow2_ens 36,
 twopoint 2, qg_spectral.hip 0), and qg_pcg.hip's 22 identical, qg_ensemble.hip 0 functions
-(profiles/spec_plan/isa_diff.txt).
+(profiles/spec_plan/isa_diff.txt).  The time statistics (qg_mi355_tstats.h) left all 261 functions
+of the earlier files identical and added the 7 of qg_tstats.hip (profiles/tstats/isa_diff.txt).
 """
 import re
 import sys
